@@ -1,6 +1,7 @@
 """Benchmark: grasp-pose IK solves/sec (Nextage dual-arm) on 1..8 MI355X.
 
     python bench.py [--gpus N --steps K --warmup W --batch B --dtype f64|f32]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 `--gpus N > 1` without a launcher (WORLD_SIZE unset) starts the N rank
@@ -19,7 +20,24 @@ unit); all problems/s is reported beside it.  The dominant kernel's roofline
 is VALU (fp64/fp32 vector ALU, no MFMA, negligible HBM traffic) — see
 DESIGN.md §5; the HBM figure the north star asks for is `roofline_hbm`.
 
-The same JSON line carries, under `extra` (timed after the headline):
+A plain run does what the headline needs and no more: set up, warm up, time
+the `--steps` steps, write the outputs if asked, print the JSON line
+(`ms_per_step` = wall milliseconds of one timed step).  Its roofline blocks
+are arithmetic over the timed steps and the committed profiles/ figures.
+(Options of their own add runs of their own: `--multistart` one untimed
+expanded solve for the update counts, `--gpus N > 1` the gather timed alone.)
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of
+the timed path receives it: `DIR/q.npy`, `converged.npy`, `iters.npy`,
+`err.npy` (and `best.npy` with `--multistart`), rank 0's batch, in the run's
+precision (float64 for f64, float32 for f32; flags and counts cast to it).
+The inputs are seeded, so two builds run with the same arguments can be
+compared output for output.  Above DUMP_BUDGET bytes in all, a fixed seeded
+sample of the rows is written and `rows.npy` holds their indices.
+
+`--full` adds everything else the benchmark measures: the CPU baselines
+(`cpu_baseline`; `--no-cpu-baseline` drops them again) and, under `extra`
+(timed after the headline; `--no-extra` drops them again):
   * `c4_strong`: BASELINE configs[3], 1,048,576 targets split over the ranks
     (strong scaling), each step the shard solves plus the RCCL gather of q,
     flags and update counts to rank 0 (ikgrasp.parallel);
@@ -51,6 +69,26 @@ F_ITER = 3144  # FP ops per IK iteration of the reference formulation (SURVEY.md
 PEAK_VALU = {"f64": 78.6, "f32": 157.3}
 PEAK_HBM = 8000.0  # GB/s (MI355X_MICROARCH.md)
 C4_TOTAL = 1 << 20  # BASELINE configs[3]
+DUMP_BUDGET = 48 << 20  # bytes --dump-outputs writes at most, all arrays together
+
+
+def dump_outputs(path, arrays, dtype):
+    """Write the timed path's outputs (`arrays`: name -> [B, ...] tensor) as
+    <path>/<name>.npy in the run's precision.  A batch whose arrays exceed
+    DUMP_BUDGET is written as a fixed sample of its rows (seed 0, ascending),
+    the same rows of every array, with their indices in rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    npdt = np.float64 if dtype == "f64" else np.float32
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(int(np.prod(a.shape[1:])) for a in arrays.values()) * np.dtype(npdt).itemsize + 8
+    keep = DUMP_BUDGET // row_bytes
+    rows = None
+    if n > keep:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a if rows is None else a[rows], dtype=npdt))
 
 
 # ---------------------------------------------------------------- host / CPU
@@ -517,8 +555,12 @@ def main():
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--yaw", type=float, default=0.0, help="random yaw range (rad) of the cube targets")
     ap.add_argument("--no-gather", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the c4_strong / c2_collision extras")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baselines and the c4_strong / c2_collision / c2_yaw extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the c4_strong / c2_collision extras")
     ap.add_argument("--variant", type=int, default=0)
     ap.add_argument("--multistart", type=int, default=0,
                     help="seeds per target (BASELINE configs[4]): every target solved from S random seeds, "
@@ -527,6 +569,10 @@ def main():
                     help="reference `success` with the collision term (inverse_geometry.py:70, :97-98) as the "
                          "headline; value counts collision-free converged solves/s")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: the headline only
+        args.no_cpu_baseline = args.no_extra = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -607,6 +653,11 @@ def main():
 
     elapsed, kern_ms = timed(torch, dist, world, args.steps, args.warmup, step, stream, drain=gather.drain)
     per = per_rank(torch, dist, world, host, dev, [kern_ms])
+    if args.dump_outputs and rank == 0:
+        last = {"q": gather.bufs[(gather.k - 1) % len(gather.bufs)], "converged": conv, "iters": iters, "err": err}
+        if S:
+            last["best"] = best
+        dump_outputs(args.dump_outputs, last, args.dtype)
 
     def gather_once():
         if host:
@@ -684,7 +735,7 @@ def main():
                 "seeds_per_target": S or 1,
                 "batch_per_gpu": B, "global_batch": B * world, "yaw_range": args.yaw,
                 "parallelism": parallelism, "world_size_seen": world, "backend": backend if world > 1 else None,
-                "devices_visible": ndev,
+                "devices_visible": ndev, "full": bool(args.full),
             },
             "problems_per_s": tot_B / per_step,
             "converged_fraction": tot_conv / tot_B,

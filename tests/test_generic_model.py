@@ -23,7 +23,6 @@ from oracle import ik_oracle as ik
 
 ROBOT = os.path.join(GOLDEN, "tilted_dualarm.urdf")
 CUBE = os.path.join(GOLDEN, "tilted_cube.urdf")
-REF = "/root/reference"
 
 
 @pytest.fixture(scope="module")
@@ -114,12 +113,10 @@ def test_emulated_kernel_solves_tilted_robot(model, gc, variant):
 
 
 def test_generic_oracle_reproduces_kats(kat):
-    """The raw-axis restatement on the reference's own URDF gives KAT-1/2."""
-    urdf = os.path.join(REF, "models/nextagea_description/urdf/NextageaOpen.urdf")
-    if not os.path.exists(urdf):
-        pytest.skip("reference tree not present")
-    m = go.ChainModel(urdf, (np.eye(3), np.array([0.0, 0.0, 0.85])))
-    hooks = go.cube_hooks(os.path.join(REF, "models/cubes/cube_small.urdf"))
+    """The raw-axis restatement on the reference's own URDF (stored copies:
+    tests/golden/NextageaOpen.urdf, cube_small.urdf) gives KAT-1/2."""
+    m = go.ChainModel(os.path.join(GOLDEN, "NextageaOpen.urdf"), (np.eye(3), np.array([0.0, 0.0, 0.85])))
+    hooks = go.cube_hooks(os.path.join(GOLDEN, "cube_small.urdf"))
     for key, qk, n in (("cube_placement", "q0", 740), ("cube_placement_target", "qe", 736)):
         q, ok, it, _ = go.computeqgrasppose(m, hooks, np.zeros(15), np.array(kat[key]["R"]), np.array(kat[key]["t"]))
         assert ok and it == n and np.abs(q - np.array(kat[qk])).max() < 1e-14

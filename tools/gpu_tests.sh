@@ -27,7 +27,7 @@ if [ "${SMOKE:-0}" = 1 ]; then
   rc=$?; echo "smoke rc=$rc"; tail -1 $O/smoke.log; [ $rc -eq 0 ] || exit $rc
 fi
 if [ "${BENCH:-0}" = 1 ]; then
-  timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err
+  timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err
   rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || exit $rc
   python -c "import json; d=json.load(open('$O/bench.json')); print('C2', round(d['ms_per_step'], 4), 'ms', round(d['value'] / 1e6, 3), 'M/s')"
 fi

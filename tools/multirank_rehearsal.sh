@@ -5,7 +5,7 @@ set -o pipefail
 mkdir -p gpurun_out/multirank
 for n in 2 4; do
   IKG_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
-    --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --gpus $n --steps 5 --warmup 1 \
+    --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --full --gpus $n --steps 5 --warmup 1 \
     > gpurun_out/multirank/n$n.json 2> gpurun_out/multirank/n$n.err || exit $?
   IKG_BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
     --master-addr 127.0.0.1 --master-port $((29510 + n)) bench.py --gpus $n --steps 3 --warmup 1 --batch 512 --multistart 64 \

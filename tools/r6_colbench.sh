@@ -8,5 +8,5 @@ b() { n=$1; shift; timeout -k 10 300 python bench.py --no-cpu-baseline --no-extr
 b c2col --collision --steps 20
 b c3col_f32 --collision --dtype f32 --batch 65536
 b c5col_f32 --collision --multistart 256 --batch 512 --dtype f32 --steps 5
-timeout -k 10 400 python bench.py > $O/bench_c2.json 2>> $O/bench.err || exit 1
+timeout -k 10 400 python bench.py --full > $O/bench_c2.json 2>> $O/bench.err || exit 1
 echo ALLDONE

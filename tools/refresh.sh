@@ -6,7 +6,7 @@ fatal() { case $1 in 0) return 0;; *) echo "FATAL $2 rc=$1" | tee -a $O/summary.
 IKG_REPORT_DIR=$O/reports timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread > $O/pytest_gpu.log 2>&1; rc=$?
 grep -E "passed|failed" $O/pytest_gpu.log | tail -1 | tee -a $O/summary.txt; [ $rc -le 1 ] || exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; fatal $? smoke
-timeout -k 10 400 python bench.py > $O/bench_c2.json 2> $O/bench.err; fatal $? bench
+timeout -k 10 400 python bench.py --full > $O/bench_c2.json 2> $O/bench.err; fatal $? bench
 b() { n=$1; shift; timeout -k 10 300 python bench.py --no-cpu-baseline --no-extra "$@" > $O/bench_$n.json 2>> $O/bench.err; fatal $? $n; }
 b c3_f32 --dtype f32 --batch 65536
 b c3_f64 --dtype f64 --batch 65536
