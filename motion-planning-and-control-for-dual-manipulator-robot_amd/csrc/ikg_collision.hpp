@@ -16,7 +16,13 @@ namespace ikg {
 
 constexpr int kMaxGeoms = 64;
 constexpr int kMaxPairs = 1024;
-constexpr int kGjkIters = 48;
+// Boolean GJK's iteration cap.  A curved pair near contact needs a direction
+// within sqrt(2 g / R) of the contact normal before a support plane separates
+// (g = 1e-7 m, R = 0.05 m: 2e-3 rad) and the simplex closes in on it by a
+// constant factor per step: at 48 steps separated cylinder pairs up to 1e-6 m
+// apart ran into the cap and its "touching" answer; 96 resolves every
+// constructed pair from 1e-7 m (tests/test_primitives.py).
+constexpr int kGjkIters = 96;
 
 enum { kSphere = 0, kBox = 1, kCylinder = 2, kMeshBox = 3 };
 
@@ -578,10 +584,14 @@ IKG_HD inline void closest_tri(const T* a, const T* b, const T* c, T* v, int& re
     for (int i = 0; i < 3; ++i) v[i] = b[i] + w_ * (c[i] - b[i]);
     return;
   }
-  const T den = T(1) / (va + vb + vc);
-  const T u = vb * den, w_ = vc * den;
+  // Face region: the foot of the origin on the plane, n (n.a) / (n.n).  The
+  // barycentric sum a + u ab + w ac carries the coordinates' rounding along
+  // the plane: on a sliver (edges 0.4 m, height 1e-5 m: a cylinder's side or
+  // a box face against a curved feature) that is ~1e-8 m, which |v| then
+  // cannot go below.
   region = 6;
-  for (int i = 0; i < 3; ++i) v[i] = a[i] + ab[i] * u + ac[i] * w_;
+  const T f = dot3(n, a) / dot3(n, n);
+  for (int i = 0; i < 3; ++i) v[i] = f * n[i];
 }
 
 // Reduce S (a triangle, w[0..2]) to the supporting feature of its closest point.
@@ -660,6 +670,15 @@ IKG_HD inline bool closest_tet_reduce(DSimplex<T>& S, T* v) {
   return false;
 }
 
+// Distance GJK.  v is the simplex's closest point to the origin and w the
+// support point of A - B towards the origin, so max(v.w, 0) / |v| <= distance
+// <= |v|: a positive v.w proves the shapes separated, and the loop
+// ends when the two bounds meet.  Without a proof the shapes touch or
+// intersect as far as the iteration resolves and the distance is 0: |v| alone
+// is only an upper bound (a curved pair 1e-9 m deep leaves |v| > 0 at any
+// iteration count).
+constexpr int kGjkDistIters = 256;
+
 template <typename T>
 IKG_HD inline T gjk_distance_raw(const Shape<T>& A, const Shape<T>& B) {
   DSimplex<T> S;
@@ -672,12 +691,15 @@ IKG_HD inline T gjk_distance_raw(const Shape<T>& A, const Shape<T>& B) {
   S.n = 1;
   cp3(v, S.w[0]);
   const T eps_rel = sizeof(T) == 8 ? T(1e-12) : T(1e-6);
-  for (int it = 0; it < 64; ++it) {
+  bool sep = false;
+  for (int it = 0; it < kGjkDistIters; ++it) {
     const T vv = dot3(v, v);
     if (vv <= (sizeof(T) == 8 ? T(1e-30) : T(1e-14))) return T(0);  // origin on the simplex: touching
     T d[3] = {-v[0], -v[1], -v[2]}, w[3];
     mink_support(A, B, d, w);
-    if (vv - dot3(v, w) <= eps_rel * vv) break;  // no progress towards the origin: |v| is the distance
+    const T vw = dot3(v, w);
+    if (vw > T(0)) sep = true;
+    if (vv - vw <= eps_rel * vv) break;  // no progress towards the origin: |v| is the distance
     // the new point is never already in the simplex once it made progress
     cp3(S.w[S.n == 1 ? 1 : (S.n == 2 ? 2 : 3)], w);
     S.n += 1;
@@ -692,12 +714,32 @@ IKG_HD inline T gjk_distance_raw(const Shape<T>& A, const Shape<T>& B) {
     if (!(dot3(vn, vn) < vv)) break;  // rounding stall: keep the best point found
     cp3(v, vn);
   }
-  return sqrt(dot3(v, v));
+  return sep ? sqrt(dot3(v, v)) : T(0);
 }
 
 // distance of one pair (min_distance of hpp-fcl's DistanceResult)
 template <typename T>
 IKG_HD inline T pair_distance(const Shape<T>& A, const Shape<T>& B) {
+  // fp32 shapes are measured in fp64 (as ikg_distance_kernel does whatever its
+  // I/O type): in fp32 the simplex tests' thresholds sit below the rounding of
+  // their own operands -- closest_tet_reduce's flat test (vol^2 <= 1e-24 l^3)
+  // let four coplanar box corners, whose volume rounds to ~1e-6 l^1.5, pass for
+  // a tetrahedron holding the origin, and shapes 0.1 m apart came out touching.
+  if constexpr (sizeof(T) == 4) {
+    double P[2][12], D[2][3];
+    for (int i = 0; i < 9; ++i) {
+      P[0][i] = (double)A.R[i];
+      P[1][i] = (double)B.R[i];
+    }
+    for (int i = 0; i < 3; ++i) {
+      P[0][9 + i] = (double)A.t[i];
+      P[1][9 + i] = (double)B.t[i];
+      D[0][i] = (double)A.dims[i];
+      D[1][i] = (double)B.dims[i];
+    }
+    const Shape<double> A2{P[0], P[0] + 9, D[0], A.kind}, B2{P[1], P[1] + 9, D[1], B.kind};
+    return (T)pair_distance(A2, B2);
+  }
   if (A.kind == kSphere && B.kind == kSphere) {
     T d[3] = {A.t[0] - B.t[0], A.t[1] - B.t[1], A.t[2] - B.t[2]};
     return sqrt(dot3(d, d)) - A.dims[0] - B.dims[0];

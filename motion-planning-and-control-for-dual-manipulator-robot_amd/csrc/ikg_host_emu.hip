@@ -326,6 +326,49 @@ extern "C" int ikg_emu_epa(int kindA, const double* RA, const double* tA, const 
   return 0;
 }
 
+// Narrow phase of n shape pairs (tests/test_primitives.py): kinds [n],
+// placements [n][12] = R (row-major) then t, dims [n][3], as in
+// ikg_collision_desc.  The placements and dimensions are rounded to the
+// dtype as build_kcollision rounds the scene tables; hit = pair_collides<T>,
+// dist = pair_distance<T>, dist_query = pair_distance<double> on the rounded
+// values (what ikg_distance_kernel evaluates whatever its I/O type).
+template <typename T>
+void emu_pairs(int64_t n, const int32_t* kindA, const double* PA, const double* dA, const int32_t* kindB,
+               const double* PB, const double* dB, uint8_t* hit, double* dist, double* dist_query) {
+  using namespace ikg;
+  for (int64_t i = 0; i < n; ++i) {
+    T Pa[12], Pb[12], da[3], db[3];
+    double Pa2[12], Pb2[12], da2[3], db2[3];
+    for (int k = 0; k < 12; ++k) {
+      Pa[k] = (T)PA[12 * i + k];
+      Pb[k] = (T)PB[12 * i + k];
+      Pa2[k] = (double)Pa[k];
+      Pb2[k] = (double)Pb[k];
+    }
+    for (int k = 0; k < 3; ++k) {
+      da[k] = (T)dA[3 * i + k];
+      db[k] = (T)dB[3 * i + k];
+      da2[k] = (double)da[k];
+      db2[k] = (double)db[k];
+    }
+    const Shape<T> A{Pa, Pa + 9, da, kindA[i]}, B{Pb, Pb + 9, db, kindB[i]};
+    hit[i] = pair_collides(A, B) != 0 ? 1 : 0;
+    dist[i] = (double)pair_distance(A, B);
+    const Shape<double> A2{Pa2, Pa2 + 9, da2, kindA[i]}, B2{Pb2, Pb2 + 9, db2, kindB[i]};
+    dist_query[i] = pair_distance(A2, B2);
+  }
+}
+
+extern "C" int ikg_emu_pairs(int dtype, int64_t n, const int32_t* kindA, const double* PA, const double* dA,
+                             const int32_t* kindB, const double* PB, const double* dB, uint8_t* hit, double* dist,
+                             double* dist_query) {
+  if (dtype == IKG_F64)
+    emu_pairs<double>(n, kindA, PA, dA, kindB, PB, dB, hit, dist, dist_query);
+  else
+    emu_pairs<float>(n, kindA, PA, dA, kindB, PB, dB, hit, dist, dist_query);
+  return 0;
+}
+
 // The loop's math helpers over arrays (tests/test_host_emu.py accuracy checks):
 // fn 0: cw_sincos (fp64), 1: cw_sincos (fp32), 2: the packed pair's sincos
 // (both halves), 3: atan2_upper (fp32), 4: atan2_upper (packed pair).

@@ -56,6 +56,14 @@
    np.linalg.pinv-class QR steps and every FK rotation entry moved by 0/+-1
    ulp, 8 jitter seeds: the largest distance from the numpy answer, and
    whether the update count / flag moved).
+11. `primitive_cases.npz` (`primitives`) — shape pairs whose separation is
+   known by construction (oracle/primitive_cases.py): base poses over every
+   kind pair and feature pair of {sphere, box, cylinder, mesh-box}, in both
+   orders, with the degenerate poses (spin 0, coaxial caps, vertex on vertex
+   along the diagonals, concentric centres); the tests expand the gap sweep.
+   World-fixed palettes for the synthetic scenes of the GPU leg, and one
+   scene of geometries attached to Nextage joints at seeded q (world
+   placements from the collision oracle's FK).
 """
 import json
 import os
@@ -509,6 +517,13 @@ def make_generic_cases(n_cold=24, n_warm=24, n_fk=32):
           int(conv[n_cold:].sum()), "/", n_warm, "warm converged; iters", [r[2] for r in res][:8])
 
 
+def make_primitive_cases():
+    from oracle import primitive_cases
+    d = primitive_cases.make()
+    np.savez_compressed(os.path.join(HERE, "primitive_cases.npz"), **d)
+    print("wrote primitive_cases.npz:", len(d["kindA"]), "world rows,", len(d["rob_kindA"]), "robot rows")
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["kat", "cases", "scene", "collision", "collision_solve", "planner", "control", "generic"]
     if os.path.isdir(REF) and "kat" in what:
@@ -531,3 +546,5 @@ if __name__ == "__main__":
         make_sensitive_cases()
     if "singular" in what:
         make_singular_cases()
+    if "primitives" in what:
+        make_primitive_cases()
