@@ -51,6 +51,25 @@ class FKOut(C.Structure):  # ikg_frame_kin_out
     _fields_ = [(n, _vp) for n in ("placement", "velocity", "J", "dJ", "dJv", "err", "derr")]
 
 
+class IDesc(C.Structure):  # ikg_inertia_desc
+    _fields_ = [("mass", C.c_double * MAXNQ), ("com", (C.c_double * 3) * MAXNQ),
+                ("inertia", (C.c_double * 6) * MAXNQ), ("gravity", C.c_double * 3)]
+
+
+class DynOut(C.Structure):  # ikg_dynamics_out
+    _fields_ = [(n, _vp) for n in ("M", "nle", "g")]
+
+
+class CtlParams(C.Structure):  # ikg_control_params
+    _fields_ = [("Kp", C.c_double), ("Kv", C.c_double), ("Kf", C.c_double), ("Kt", C.c_double),
+                ("lambda_reg", C.c_double), ("qp_reg", C.c_double), ("fc_bias", C.c_double * 12),
+                ("zero_tau_mask", C.c_uint32)]
+
+
+class CtlOut(C.Structure):  # ikg_control_out
+    _fields_ = [(n, _vp) for n in ("tau", "qdd", "xdd", "Lambda", "fc")]
+
+
 _lib = None
 
 
@@ -68,6 +87,13 @@ def lib():
                                          C.c_uint32]
         L.ikg_frame_kinematics_batch.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int64, C.c_int,
                                                  C.POINTER(FKOut), _vp, C.c_uint32]
+        L.ikg_model_set_inertia.argtypes = [_vp, C.POINTER(IDesc)]
+        L.ikg_dynamics_batch.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int64, C.POINTER(DynOut), _vp,
+                                         C.c_uint32]
+        L.ikg_control_params_default.argtypes = [C.POINTER(CtlParams)]
+        L.ikg_control_params_default.restype = None
+        L.ikg_control_torque_batch.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int64, C.POINTER(CtlParams),
+                                               C.POINTER(CtlOut), _vp, C.c_uint32]
         L.ikg_last_error.restype = C.c_char_p
         _lib = L
     return _lib
@@ -202,3 +228,57 @@ def task_space_terms(q, vq, q_des, vq_des):
     if rc != 0:
         raise RuntimeError(lib().ikg_last_error().decode())
     return J, Jdv, e, ed
+
+
+def _idesc(robot):
+    """robot.model.inertias (joint frames; the URDF loader's merged bodies) + model.gravity -> ikg_inertia_desc."""
+    m, d = robot.model, IDesc()
+    for j in range(1, m.njoints):
+        Y = m.inertias[j]
+        I = np.asarray(Y.inertia, dtype=np.float64)
+        d.mass[j - 1] = Y.mass
+        d.com[j - 1][:] = list(np.asarray(Y.lever, dtype=np.float64))
+        d.inertia[j - 1][:] = [I[0, 0], I[0, 1], I[0, 2], I[1, 1], I[1, 2], I[2, 2]]
+    d.gravity[:] = list(np.asarray(m.gravity.linear, dtype=np.float64))
+    return d
+
+
+_has_inertia = False
+
+
+def _dynamic_model(robot, cube):
+    global _has_inertia
+    model = _model_for(robot, cube)
+    if not _has_inertia:
+        if lib().ikg_model_set_inertia(model, C.byref(_idesc(robot))) != 0:
+            raise RuntimeError(lib().ikg_last_error().decode())
+        _has_inertia = True
+    return model
+
+
+def dynamics_terms(robot, cube, q, vq):
+    """control.py:284-286 -> (M [nq,nq], b [nq]): data.M after computeAllTerms and pin.nonLinearEffects."""
+    nq = robot.model.nq
+    q, vq = np.ascontiguousarray(q, dtype=np.float64), np.ascontiguousarray(vq, dtype=np.float64)
+    M, b = np.empty((nq, nq)), np.empty(nq)
+    out = DynOut(M.ctypes.data, b.ctypes.data, None)
+    if lib().ikg_dynamics_batch(_dynamic_model(robot, cube), 0, 0, q.ctypes.data, vq.ctypes.data, 1, C.byref(out),
+                                None, 1) != 0:
+        raise RuntimeError(lib().ikg_last_error().decode())
+    return M, b
+
+
+def controllaw(sim, robot, trajs, tcurrent, cube):
+    """Drop-in for control.controllaw (:242-410): the torques of :284-406 in one call, then sim.step."""
+    q, vq = sim.getpybulletstate()                                  # :254
+    f = lambda x: np.ascontiguousarray(x, dtype=np.float64)  # noqa: E731
+    q, vq, q_des, vq_des = f(q), f(vq), f(trajs[0](tcurrent)), f(trajs[1](tcurrent))   # :269-270
+    tau = np.empty(robot.model.nq)
+    p = CtlParams()
+    lib().ikg_control_params_default(C.byref(p))                     # :248-251, :349, :375, :386, :404
+    out = CtlOut(tau.ctypes.data, None, None, None, None)
+    rc = lib().ikg_control_torque_batch(_dynamic_model(robot, cube), 0, q.ctypes.data, vq.ctypes.data,
+                                        q_des.ctypes.data, vq_des.ctypes.data, 1, C.byref(p), C.byref(out), None, 1)
+    if rc != 0:
+        raise RuntimeError(lib().ikg_last_error().decode())
+    sim.step(tau.tolist())                                          # :410

@@ -336,6 +336,92 @@ int ikg_frame_kinematics_batch(const ikg_model* model, int device, int dtype, co
                                const void* q_des, const void* v_des, int64_t B, int rf,
                                const ikg_frame_kin_out* out, void* stream, uint32_t flags);
 
+/*
+ * Controller dynamics: M and b of control.py:284-286 for a batch of states.
+ * Replaces
+ *   pin.computeAllTerms(model, data, q, vq); M = data.M      (control.py:284-285)
+ *   b = pin.nonLinearEffects(model, data, q, vq)             (:286)
+ * for any joint tree ikg_model_create accepts (passive joints may hang
+ * anywhere).  The body inertias are attached with ikg_model_set_inertia: per
+ * joint in q order the inertia of the body it moves -- its child link plus
+ * every link fixed to it, as Pinocchio's URDF loader merges them -- in the
+ * model's (canonical) joint frame.  mass >= 0; the inertia about the centre of
+ * mass must be positive semi-definite with principal moments obeying the
+ * triangle inequalities, else IKG_EINVAL.  gravity is in the world frame
+ * (Pinocchio's model.gravity and setup_pybullet.py:33: (0, 0, -9.81)).
+ *   q, v [B,nq] (v NULL = zero velocity).  Every output is optional (NULL):
+ *   M    [B,nq,nq]  joint-space inertia matrix, both triangles filled
+ *                   (data.M after computeAllTerms, symmetrised: the controller
+ *                   inverts it and multiplies by it, :348, :401)
+ *   nle  [B,nq]     pin.nonLinearEffects = C(q,v) v + g(q)
+ *   g    [B,nq]     nle at zero velocity (pin.computeGeneralizedGravity)
+ * Without attached inertias the call returns IKG_EINVAL.  Host-pointer calls
+ * check q and v for finiteness; B == 0 is a no-op.  Stream-ordered, no
+ * scratch memory, capturable like the other entries.
+ */
+typedef struct ikg_inertia_desc {
+  double mass[IKG_MAX_NQ];
+  double com[IKG_MAX_NQ][3];     /* in the (canonical) joint frame */
+  double inertia[IKG_MAX_NQ][6]; /* xx xy xz yy yz zz about the com, joint-frame axes */
+  double gravity[3];             /* world frame */
+} ikg_inertia_desc;
+int ikg_model_set_inertia(ikg_model* model, const ikg_inertia_desc* desc);
+
+typedef struct ikg_dynamics_out {
+  void* M;
+  void* nle;
+  void* g;
+} ikg_dynamics_out;
+int ikg_dynamics_batch(const ikg_model* model, int device, int dtype, const void* q, const void* v, int64_t B,
+                       const ikg_dynamics_out* out, void* stream, uint32_t flags);
+
+/*
+ * The controller's torques: the second half of controllaw, control.py:284-406,
+ * for a batch of states with no host round trip: the kinematic terms of
+ * ikg_frame_kinematics_batch (LOCAL_WORLD_ALIGNED) and M, nle of
+ * ikg_dynamics_batch go to device scratch from the model's workspace pool, then
+ * one solve kernel does, per state and per hand h (rows 0-5 LARM_EFF, 6-11 RARM_EFF):
+ *   Lambda_h = (J_h M^-1 J_h^T + lambda_reg 1)^-1                        (:348-349)
+ *   fc_h = [Kf e_t; Kt e_r];  xdd_h = Kp e + Kv e' + Lambda_h fc_h      (:338-360)
+ *   qdd = (J^T J + qp_reg 1)^-1 J^T (xdd - dJ v)                        (:381-395)
+ *     quadprog.solve_qp(H, d) without constraints minimises 1/2 x^T H x - d^T x,
+ *     i.e. x = H^-1 d with d = -J^T (dJ v - xdd) after the reference's d_qp = -d_qp
+ *   tau = M qdd + nle + J^T (fc + fc_bias); tau[j] = 0 for j in zero_tau_mask  (:375, :401-406)
+ * Each inverse is a Cholesky-type (L D L^T) factorisation of a symmetric
+ * positive definite matrix.  The reference's try/except -> zeros (:396-398)
+ * cannot trigger for such an H; should a pivot of H come out non-positive
+ * (non-finite input only), qdd is written as zeros as the reference would.
+ * fp64 ONLY: the 1e-6 regularisation of the rank-deficient nq x nq system
+ * (the head columns of J are zero) leaves fp32 no correct digits.
+ *   q, v, q_des, v_des [B,nq] (v, v_des NULL = zero).  Outputs, all optional:
+ *   tau    [B,nq]    what sim.step receives (:410)
+ *   qdd    [B,nq]    the QP's solution (exactly 0 where J^T(...) is exactly 0: the head joints)
+ *   xdd    [B,12]    x_ddot_des_total (:371)
+ *   Lambda [B,2,36]  per hand, row-major 6 x 6
+ *   fc     [B,12]    f_c_total BEFORE the bias (the bias enters tau only, :375, :401)
+ * Needs ikg_model_set_inertia (else IKG_EINVAL).  Host-pointer calls check the
+ * inputs for finiteness.  B == 0 is a no-op.  Stream-ordered and capturable
+ * like the other entries (scratch: "Graphs" above).
+ */
+typedef struct ikg_control_params { /* defaults = control.py:248-251, :349, :375, :386, :404 */
+  double Kp, Kv, Kf, Kt;            /* 7000, 2 sqrt(Kp), 30, 2 sqrt(Kf) */
+  double lambda_reg, qp_reg;        /* 1e-6, 1e-6 */
+  double fc_bias[12];               /* zeros except [1] = -200 */
+  uint32_t zero_tau_mask;           /* bits 1 and 2 */
+} ikg_control_params;
+void ikg_control_params_default(ikg_control_params* p);
+
+typedef struct ikg_control_out {
+  void* tau;
+  void* qdd;
+  void* xdd;
+  void* Lambda;
+  void* fc;
+} ikg_control_out;
+int ikg_control_torque_batch(const ikg_model* model, int device, const void* q, const void* v, const void* q_des,
+                             const void* v_des, int64_t B, const ikg_control_params* params,
+                             const ikg_control_out* out, void* stream, uint32_t flags);
+
 /* Thread-local message of the last failure ("" if none). */
 const char* ikg_last_error(void);
 

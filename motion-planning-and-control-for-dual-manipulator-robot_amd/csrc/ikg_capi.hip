@@ -52,6 +52,12 @@ struct ikg_model {
   ikg::KCollision<float> c32;
   std::vector<void*> col64;
   std::vector<void*> col32;
+  // body inertias and gravity (ikg_model_set_inertia)
+  bool has_inertia = false;
+  ikg::KInertia<double> i64;
+  ikg::KInertia<float> i32;
+  std::vector<void*> ine64;
+  std::vector<void*> ine32;
   // model-specialised pair kernels (ikg_model_specialize): code objects per
   // dtype (0 = f64, 1 = f32), loaded modules per device
   std::vector<char> jit_code[2];
@@ -97,6 +103,14 @@ struct ikg_model {
     if (!has_collision) return fail(IKG_EINVAL, "no collision scene attached (ikg_model_set_collision)");
     const bool d = sizeof(T) == 8;
     return upload(d ? col64 : col32, device, d ? (const void*)&c64 : (const void*)&c32, sizeof(ikg::KCollision<T>),
+                  (const void**)out);
+  }
+
+  template <typename T>
+  int inertia_tables(int device, const ikg::KInertia<T>** out) {
+    if (!has_inertia) return fail(IKG_EINVAL, "no body inertias attached (ikg_model_set_inertia)");
+    const bool d = sizeof(T) == 8;
+    return upload(d ? ine64 : ine32, device, d ? (const void*)&i64 : (const void*)&i32, sizeof(ikg::KInertia<T>),
                   (const void**)out);
   }
 };
@@ -720,6 +734,8 @@ void ikg_model_destroy(ikg_model* m) {
   free_slots(m->dev32);
   free_slots(m->col64);
   free_slots(m->col32);
+  free_slots(m->ine64);
+  free_slots(m->ine32);
   for (auto& v : m->jit)
     for (size_t i = 0; i < v.size(); ++i)
       if (v[i]) {
@@ -1034,6 +1050,219 @@ int ikg_frame_kinematics_batch(const ikg_model* model, int device, int dtype, co
   hipStream_t s = (hipStream_t)stream;
   return dtype == IKG_F64 ? frame_kin_t<double>(m, device, q, v, q_des, v_des, B, rf, *out, s, flags)
                           : frame_kin_t<float>(m, device, q, v, q_des, v_des, B, rf, *out, s, flags);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------ controller dynamics
+template <typename T>
+int dynamics_t(ikg_model* model, int device, const void* q, const void* v, int64_t B, const ikg_dynamics_out& out,
+               hipStream_t s, uint32_t flags) {
+  const ikg::KModel<T>* dm = nullptr;
+  int rc = model->device_tables<T>(device, &dm);
+  if (rc) return rc;
+  const ikg::KInertia<T>* di = nullptr;
+  if ((rc = model->inertia_tables<T>(device, &di))) return rc;
+  const int nq = model->desc.nq;
+  const size_t sz[3] = {(size_t)nq * nq, (size_t)nq, (size_t)nq};  // per state
+  void* host_out[3] = {out.M, out.nle, out.g};
+  void* dev_out[3];
+  Staging st(s);
+  const bool host = flags & IKG_FLAG_HOST_POINTERS;
+  const void *dq = q, *dv = v;
+  if (host) {
+    dq = st.in(q, sizeof(T) * nq * B);
+    dv = st.in(v, sizeof(T) * nq * B);
+  }
+  for (int i = 0; i < 3; ++i) dev_out[i] = host && host_out[i] ? st.out(sizeof(T) * sz[i] * B) : host_out[i];
+  if (st.rc) return st.rc;
+  const ikg::DynOut o{dev_out[0], dev_out[1], dev_out[2]};
+  hipError_t e = ikg::launch_dynamics<T>(dm, di, nq, dq, dv, B, o, s);
+  if (e != hipSuccess) return hip_fail(e, "ikg dynamics kernel launch");
+  if (host) {
+    for (int i = 0; i < 3; ++i)
+      if (host_out[i]) st.back(host_out[i], dev_out[i], sizeof(T) * sz[i] * B);
+    if (st.rc) return st.rc;
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+  }
+  return IKG_OK;
+}
+
+extern "C" {
+
+int ikg_model_set_inertia(ikg_model* m, const ikg_inertia_desc* d) {
+  g_err[0] = 0;
+  if (!m || !d) return fail(IKG_EINVAL, "NULL argument");
+  const char* why = "";
+  const int bad = ikg::check_inertia_desc(*d, m->desc.nq, &why);
+  if (bad >= 0) return fail(IKG_EINVAL, "inertia of body %d: %s", bad, why);
+  std::lock_guard<std::mutex> lock(m->mu);
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  free_slots(m->ine64);  // re-uploaded lazily; callers must not race a launch
+  free_slots(m->ine32);
+  if (prev >= 0) (void)hipSetDevice(prev);
+  ikg::build_kinertia<double>(m->desc, *d, m->i64);
+  ikg::build_kinertia<float>(m->desc, *d, m->i32);
+  m->has_inertia = true;
+  return IKG_OK;
+}
+
+int ikg_dynamics_batch(const ikg_model* model, int device, int dtype, const void* q, const void* v, int64_t B,
+                       const ikg_dynamics_out* out, void* stream, uint32_t flags) {
+  g_err[0] = 0;
+  if (!model) return fail(IKG_EINVAL, "model is NULL");
+  if (!out) return fail(IKG_EINVAL, "out is NULL");
+  if (B < 0) return fail(IKG_EINVAL, "B must be >= 0");
+  if (dtype != IKG_F64 && dtype != IKG_F32) return fail(IKG_EINVAL, "dtype %d unknown", dtype);
+  if (B > 0 && !q) return fail(IKG_EINVAL, "q is required");
+  if (B > (int64_t)1 << 40) return fail(IKG_EINVAL, "B too large");
+  if (!model->has_inertia) return fail(IKG_EINVAL, "no body inertias attached (ikg_model_set_inertia)");
+  if (flags & IKG_FLAG_HOST_POINTERS) {  // the device code is built with -ffinite-math-only
+    const int64_t n = B * model->desc.nq;
+    int rc = dtype == IKG_F64 ? check_finite<double>(q, n, "q") : check_finite<float>(q, n, "q");
+    if (!rc && v) rc = dtype == IKG_F64 ? check_finite<double>(v, n, "v") : check_finite<float>(v, n, "v");
+    if (rc) return rc;
+  }
+  DeviceGuard g(device);
+  if (g.rc) return g.rc;
+  if (B == 0) return IKG_OK;
+  ikg_model* m = const_cast<ikg_model*>(model);
+  hipStream_t s = (hipStream_t)stream;
+  return dtype == IKG_F64 ? dynamics_t<double>(m, device, q, v, B, *out, s, flags)
+                          : dynamics_t<float>(m, device, q, v, B, *out, s, flags);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------ controller torques
+namespace {
+
+// states per pass of ikg_control_torque_batch: its scratch (M, nle, J, dJ v, e,
+// e' per state: 3.6 KB at nq = 15) stays at 240 MB whatever the batch
+constexpr int64_t kCtlChunk = 65536;
+
+int control_torque(ikg_model* model, int device, const void* q, const void* v, const void* qd, const void* vd,
+                   int64_t B, const ikg_control_params& params, const ikg_control_out& out, hipStream_t s,
+                   uint32_t flags) {
+  using T = double;
+  if (!ikg::stream_capturing(s)) ikg::ws_drain(&model->ws);  // scratch of destroyed graphs
+  const ikg::KModel<T>* dm = nullptr;
+  int rc = model->device_tables<T>(device, &dm);
+  if (rc) return rc;
+  const ikg::KInertia<T>* di = nullptr;
+  if ((rc = model->inertia_tables<T>(device, &di))) return rc;
+  const int nq = model->desc.nq;
+  const size_t sz[5] = {(size_t)nq, (size_t)nq, 12, 72, 12};  // per state
+  void* host_out[5] = {out.tau, out.qdd, out.xdd, out.Lambda, out.fc};
+  void* dev_out[5];
+  Staging st(s);
+  const bool host = flags & IKG_FLAG_HOST_POINTERS;
+  const void *dq = q, *dv = v, *dqd = qd, *dvd = vd;
+  if (host) {
+    dq = st.in(q, sizeof(T) * nq * B);
+    dv = st.in(v, sizeof(T) * nq * B);
+    dqd = st.in(qd, sizeof(T) * nq * B);
+    dvd = st.in(vd, sizeof(T) * nq * B);
+  }
+  for (int i = 0; i < 5; ++i) dev_out[i] = host && host_out[i] ? st.out(sizeof(T) * sz[i] * B) : host_out[i];
+  if (st.rc) return st.rc;
+  const int64_t chunk = std::min(B, kCtlChunk);
+  const size_t per = (size_t)nq * nq + nq + 12 * (size_t)nq + 36;
+  void* ws = nullptr;
+  hipError_t e = ikg::ws_alloc(&model->ws, &ws, sizeof(T) * per * chunk, s);
+  if (e != hipSuccess) return fail(IKG_ENOMEM, "controller scratch (%zu bytes): %s", sizeof(T) * per * chunk,
+                                   hipGetErrorString(e));
+  ikg::poison_float(ws, sizeof(T) * per * chunk, s);
+  T* wM = (T*)ws;
+  T* wJ = wM + (size_t)nq * nq * chunk;
+  T* wn = wJ + 12 * (size_t)nq * chunk;
+  T* wdJv = wn + (size_t)nq * chunk;
+  T* werr = wdJv + 12 * chunk;
+  T* wderr = werr + 12 * chunk;
+  const ikg::KCtl<T> prm = ikg::make_kctl<T>(params);
+  const char* what = "";
+  for (int64_t off = 0; off < B && e == hipSuccess; off += chunk) {
+    const int64_t n = std::min(chunk, B - off);
+    auto at = [&](const void* p, size_t w) { return p ? (const void*)((const T*)p + w * off) : nullptr; };
+    auto ao = [&](void* p, size_t w) { return p ? (void*)((T*)p + w * off) : nullptr; };
+    const ikg::FrameKinOut fo{nullptr, nullptr, wJ, nullptr, wdJv, werr, wderr};
+    what = "ikg frame kinematics kernel launch";
+    e = ikg::launch_frame_kin<T>(dm, nq, model->spec, at(dq, nq), at(dv, nq), at(dqd, nq), at(dvd, nq), n,
+                                 IKG_LOCAL_WORLD_ALIGNED, fo, s);
+    if (e != hipSuccess) break;
+    what = "ikg dynamics kernel launch";
+    e = ikg::launch_dynamics<T>(dm, di, nq, at(dq, nq), at(dv, nq), n, ikg::DynOut{wM, wn, nullptr}, s);
+    if (e != hipSuccess) break;
+    what = "ikg controller solve kernel launch";
+    const ikg::CtlIn in{wM, wn, wJ, wdJv, werr, wderr};
+    const ikg::CtlOut co{ao(dev_out[0], sz[0]), ao(dev_out[1], sz[1]), ao(dev_out[2], sz[2]), ao(dev_out[3], sz[3]),
+                         ao(dev_out[4], sz[4])};
+    e = ikg::launch_control_solve(in, nq, n, prm, co, s);
+  }
+  const hipError_t ef = ikg::ws_free(&model->ws, ws, s);
+  if (e != hipSuccess) return hip_fail(e, what);
+  if (ef != hipSuccess) return hip_fail(ef, "controller scratch free");
+  if (host) {
+    for (int i = 0; i < 5; ++i)
+      if (host_out[i]) st.back(host_out[i], dev_out[i], sizeof(T) * sz[i] * B);
+    if (st.rc) return st.rc;
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+  }
+  return IKG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void ikg_control_params_default(ikg_control_params* p) {
+  if (!p) return;
+  p->Kp = 7000.0;                // control.py:248
+  p->Kv = 2.0 * std::sqrt(p->Kp);  // :249
+  p->Kf = 30.0;                  // :250
+  p->Kt = 2.0 * std::sqrt(p->Kf);  // :251
+  p->lambda_reg = 1e-6;          // :349
+  p->qp_reg = 1e-6;              // :386
+  for (int i = 0; i < 12; ++i) p->fc_bias[i] = 0.0;
+  p->fc_bias[1] = -200.0;        // :375
+  p->zero_tau_mask = (1u << 1) | (1u << 2);  // :404
+}
+
+int ikg_control_torque_batch(const ikg_model* model, int device, const void* q, const void* v, const void* q_des,
+                             const void* v_des, int64_t B, const ikg_control_params* params,
+                             const ikg_control_out* out, void* stream, uint32_t flags) {
+  g_err[0] = 0;
+  if (!model) return fail(IKG_EINVAL, "model is NULL");
+  if (!out) return fail(IKG_EINVAL, "out is NULL");
+  if (!params) return fail(IKG_EINVAL, "params is NULL");
+  if (B < 0) return fail(IKG_EINVAL, "B must be >= 0");
+  if (B > 0 && (!q || !q_des)) return fail(IKG_EINVAL, "q and q_des are required");
+  if (B > (int64_t)1 << 40) return fail(IKG_EINVAL, "B too large");
+  if (!model->has_inertia) return fail(IKG_EINVAL, "no body inertias attached (ikg_model_set_inertia)");
+  {
+    const double g[6] = {params->Kp, params->Kv, params->Kf, params->Kt, params->lambda_reg, params->qp_reg};
+    int rc = check_finite<double>(g, 6, "gains");
+    if (!rc) rc = check_finite<double>(params->fc_bias, 12, "fc_bias");
+    if (rc) return rc;
+    if (!(params->lambda_reg > 0) || !(params->qp_reg > 0))
+      return fail(IKG_EINVAL, "lambda_reg and qp_reg must be > 0 (they make the factored matrices positive definite)");
+  }
+  if (flags & IKG_FLAG_HOST_POINTERS) {  // the device code is built with -ffinite-math-only
+    const int64_t n = B * model->desc.nq;
+    int rc = check_finite<double>(q, n, "q");
+    if (!rc && v) rc = check_finite<double>(v, n, "v");
+    if (!rc) rc = check_finite<double>(q_des, n, "q_des");
+    if (!rc && v_des) rc = check_finite<double>(v_des, n, "v_des");
+    if (rc) return rc;
+  }
+  DeviceGuard g(device);
+  if (g.rc) return g.rc;
+  if (B == 0) return IKG_OK;
+  return control_torque(const_cast<ikg_model*>(model), device, q, v, q_des, v_des, B, *params, *out,
+                        (hipStream_t)stream, flags);
 }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 
 #include "ikg_collision.hpp"
 #include "ikg_device.hpp"
+#include "ikg_dynamics.hpp"
 #include "ikg_model_build.hpp"
 #include "ikgrasp.h"
 
@@ -402,6 +403,60 @@ extern "C" int ikg_emu_math(int fn, int64_t n, const double* x, const double* y,
       }
       default: return -1;
     }
+  }
+  return 0;
+}
+
+// ikg_dynamics_batch on the CPU: the per-body functions of ikg_dynamics.hpp in
+// the kernel's order (tests/test_dynamics.py).  v and every output may be NULL.
+template <typename T>
+void emu_dyn(const ikg_model_desc* d, const ikg_inertia_desc* id, const void* q, const void* v, int64_t B, void* M,
+             void* nle, void* g) {
+  static thread_local ikg::KModel<T> m;
+  static thread_local ikg::KInertia<T> in;
+  ikg::build_kmodel<T>(*d, m);
+  ikg::build_kinertia<T>(*d, *id, in);
+  const int nq = d->nq;
+  for (int64_t i = 0; i < B; ++i)
+    ikg::dynamics_state<T>(m, in, (const T*)q + nq * i, v ? (const T*)v + nq * i : nullptr,
+                           M ? (T*)M + (int64_t)nq * nq * i : nullptr, nle ? (T*)nle + nq * i : nullptr,
+                           g ? (T*)g + nq * i : nullptr);
+}
+
+extern "C" int ikg_emu_dynamics(const ikg_model_desc* d, const ikg_inertia_desc* id, int dtype, const void* q,
+                                const void* v, int64_t B, void* M, void* nle, void* g) {
+  const char* why = "";
+  if (ikg::check_inertia_desc(*id, d->nq, &why) >= 0) return -1;
+  if (dtype == IKG_F64)
+    emu_dyn<double>(d, id, q, v, B, M, nle, g);
+  else
+    emu_dyn<float>(d, id, q, v, B, M, nle, g);
+  return 0;
+}
+
+// The solve of ikg_control_torque_batch on the CPU (fp64): M and nle from
+// dynamics_state, then the phases of control_state; the kinematic terms J
+// [B,12,nq], dJv, err, derr [B,12] (ikg_frame_kinematics_batch,
+// LOCAL_WORLD_ALIGNED) are inputs.  Outputs may be NULL.
+extern "C" int ikg_emu_control_torque(const ikg_model_desc* d, const ikg_inertia_desc* id, const double* q,
+                                      const double* v, const double* J, const double* dJv, const double* err,
+                                      const double* derr, int64_t B, const ikg_control_params* p, double* tau,
+                                      double* qdd, double* xdd, double* Lambda, double* fc) {
+  const char* why = "";
+  if (ikg::check_inertia_desc(*id, d->nq, &why) >= 0) return -1;
+  static thread_local ikg::KModel<double> m;
+  static thread_local ikg::KInertia<double> in;
+  ikg::build_kmodel<double>(*d, m);
+  ikg::build_kinertia<double>(*d, *id, in);
+  const ikg::KCtl<double> prm = ikg::make_kctl<double>(*p);
+  const int nq = d->nq;
+  for (int64_t i = 0; i < B; ++i) {
+    double M[ikg::kMaxNq * ikg::kMaxNq], nle[ikg::kMaxNq];
+    ikg::dynamics_state<double>(m, in, q + nq * i, v ? v + nq * i : nullptr, M, nle, nullptr);
+    ikg::control_state<double>(nq, prm, M, nle, J + 12 * nq * i, dJv + 12 * i, err + 12 * i, derr + 12 * i,
+                               tau ? tau + nq * i : nullptr, qdd ? qdd + nq * i : nullptr,
+                               xdd ? xdd + 12 * i : nullptr, Lambda ? Lambda + 72 * i : nullptr,
+                               fc ? fc + 12 * i : nullptr);
   }
   return 0;
 }

@@ -14,6 +14,7 @@
 
 #include "ikg_collision.hpp"
 #include "ikg_device.hpp"
+#include "ikg_dynamics.hpp"
 #include "ikg_solve.hpp"
 
 namespace ikg {
@@ -479,5 +480,35 @@ template <typename T>
 hipError_t launch_frame_kin(const KModel<T>* dm, int nq, int spec, const void* q, const void* v, const void* qd,
                             const void* vd,
                             int64_t B, int rf, const FrameKinOut& o, hipStream_t s);
+
+// controller dynamics (control.py:284-286, ikg_dynamics.hip): optional outputs
+struct DynOut {
+  void* M;    // [B,nq,nq]
+  void* nle;  // [B,nq]
+  void* g;    // [B,nq]
+};
+template <typename T>
+hipError_t launch_dynamics(const KModel<T>* dm, const KInertia<T>* di, int nq, const void* q, const void* v,
+                           int64_t B, const DynOut& o, hipStream_t s);
+
+// controller solve (control.py:348-406, ikg_dynamics.hip): per-state inputs
+// (device, fp64) and optional outputs
+struct CtlIn {
+  const void* M;     // [B,nq,nq]
+  const void* nle;   // [B,nq]
+  const void* J;     // [B,12,nq]
+  const void* dJv;   // [B,12]
+  const void* err;   // [B,12]
+  const void* derr;  // [B,12]
+};
+struct CtlOut {
+  void* tau;     // [B,nq]
+  void* qdd;     // [B,nq]
+  void* xdd;     // [B,12]
+  void* Lambda;  // [B,2,36]
+  void* fc;      // [B,12]
+};
+hipError_t launch_control_solve(const CtlIn& in, int nq, int64_t B, const KCtl<double>& prm, const CtlOut& o,
+                                hipStream_t s);
 
 }  // namespace ikg

@@ -80,11 +80,42 @@ class FrameKinOut(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("placement", "velocity", "J", "dJ", "dJv", "err", "derr")]
 
 
+class InertiaDesc(C.Structure):
+    """ikg_inertia_desc: per-joint body inertias (ikg_model_set_inertia)."""
+    _fields_ = [
+        ("mass", C.c_double * IKG_MAX_NQ),
+        ("com", (C.c_double * 3) * IKG_MAX_NQ),
+        ("inertia", (C.c_double * 6) * IKG_MAX_NQ),
+        ("gravity", C.c_double * 3),
+    ]
+
+
+class DynamicsOut(C.Structure):
+    """ikg_dynamics_out: optional output pointers of ikg_dynamics_batch."""
+    _fields_ = [(name, C.c_void_p) for name in ("M", "nle", "g")]
+
+
+class ControlParams(C.Structure):
+    """ikg_control_params: gains and constants of control.py:248-251, :349, :375, :386, :404."""
+    _fields_ = [
+        ("Kp", C.c_double), ("Kv", C.c_double), ("Kf", C.c_double), ("Kt", C.c_double),
+        ("lambda_reg", C.c_double), ("qp_reg", C.c_double),
+        ("fc_bias", C.c_double * 12),
+        ("zero_tau_mask", C.c_uint32),
+    ]
+
+
+class ControlOut(C.Structure):
+    """ikg_control_out: optional output pointers of ikg_control_torque_batch."""
+    _fields_ = [(name, C.c_void_p) for name in ("tau", "qdd", "xdd", "Lambda", "fc")]
+
+
 EXPORTS = [
     "ikg_model_create", "ikg_model_destroy", "ikg_params_default", "ikg_solve_batch",
     "ikg_solve_multistart", "ikg_fk_batch", "ikg_log6_batch", "ikg_last_error", "ikg_version",
     "ikg_model_set_collision", "ikg_collision_batch", "ikg_distance_batch", "ikg_target_env_batch",
     "ikg_frame_kinematics_batch", "ikg_model_specialize", "ikg_model_is_specialized", "ikg_model_trim",
+    "ikg_model_set_inertia", "ikg_dynamics_batch", "ikg_control_params_default", "ikg_control_torque_batch",
 ]
 
 _lib = None
@@ -148,6 +179,15 @@ def load() -> C.CDLL:
     lib.ikg_frame_kinematics_batch.argtypes = [vp, i32, i32, vp, vp, vp, vp, i64, i32, C.POINTER(FrameKinOut), vp,
                                                C.c_uint32]
     lib.ikg_frame_kinematics_batch.restype = i32
+    lib.ikg_model_set_inertia.argtypes = [vp, C.POINTER(InertiaDesc)]
+    lib.ikg_model_set_inertia.restype = i32
+    lib.ikg_dynamics_batch.argtypes = [vp, i32, i32, vp, vp, i64, C.POINTER(DynamicsOut), vp, C.c_uint32]
+    lib.ikg_dynamics_batch.restype = i32
+    lib.ikg_control_params_default.argtypes = [C.POINTER(ControlParams)]
+    lib.ikg_control_params_default.restype = None
+    lib.ikg_control_torque_batch.argtypes = [vp, i32, vp, vp, vp, vp, i64, C.POINTER(ControlParams),
+                                             C.POINTER(ControlOut), vp, C.c_uint32]
+    lib.ikg_control_torque_batch.restype = i32
     lib.ikg_model_specialize.argtypes = [vp, i32, i32, C.c_uint32]
     lib.ikg_model_specialize.restype = i32
     lib.ikg_model_is_specialized.argtypes = [vp, i32, i32]
@@ -209,6 +249,41 @@ def collision_desc(scene) -> CollisionDesc:
         d.pairs[k][0] = int(a)
         d.pairs[k][1] = int(b)
     return d
+
+
+def inertia_desc(inertias, gravity=(0.0, 0.0, -9.81)) -> InertiaDesc:
+    """ikgrasp.model.BodyInertias (+ world-frame gravity) -> ikg_inertia_desc."""
+    if inertias.nq > IKG_MAX_NQ:
+        raise ValueError(f"{inertias.nq} bodies (max {IKG_MAX_NQ})")
+    d = InertiaDesc()
+    for i in range(inertias.nq):
+        d.mass[i] = float(inertias.mass[i])
+        d.com[i][:] = [float(x) for x in inertias.com[i]]
+        d.inertia[i][:] = [float(x) for x in inertias.inertia[i]]
+    d.gravity[:] = [float(x) for x in gravity]
+    return d
+
+
+def control_params(**gains) -> ControlParams:
+    """ikg_control_params_default with overrides: Kp, Kv, Kf, Kt, lambda_reg,
+    qp_reg, fc_bias (12 numbers), zero_tau (joint indices) or zero_tau_mask."""
+    p = ControlParams()
+    load().ikg_control_params_default(C.byref(p))
+    for k, v in gains.items():
+        if k == "fc_bias":
+            b = [float(x) for x in np.asarray(v, dtype=np.float64).reshape(-1)]
+            if len(b) != 12:
+                raise ValueError("fc_bias must hold 12 numbers")
+            p.fc_bias[:] = b
+        elif k == "zero_tau":
+            p.zero_tau_mask = sum(1 << int(j) for j in set(v))
+        elif k in ("Kp", "Kv", "Kf", "Kt", "lambda_reg", "qp_reg"):
+            setattr(p, k, float(v))
+        elif k == "zero_tau_mask":
+            p.zero_tau_mask = int(v)
+        else:
+            raise ValueError(f"unknown controller parameter {k!r}")
+    return p
 
 
 def default_params(**overrides) -> Params:

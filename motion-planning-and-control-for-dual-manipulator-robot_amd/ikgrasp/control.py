@@ -15,9 +15,13 @@ spends its kinematic work, per tick, in Pinocchio calls over the two hands:
 
 `task_space_terms` returns those stacked quantities for one state (the
 drop-in for that block); `task_space_terms_batch` does many states in one
-launch of `ikg_frame_kinematics_batch` (GPU).  The dynamics (M, b from
-computeAllTerms / nonLinearEffects), the QP (quadprog) and the simulator stay
-out of scope.  There is no CPU path: without the HIP library
+launch of `ikg_frame_kinematics_batch` (GPU).  `dynamics_terms_batch` gives
+the dynamics of :284-286 (M from computeAllTerms, b from nonLinearEffects)
+for many states in one launch of `ikg_dynamics_batch`, and
+`control_torques_batch` the whole second half of the law (:284-406: the
+operational-space inertia, the unconstrained QP and the torque line) through
+`ikg_control_torque_batch`.  `controllaw` is the drop-in for the reference
+function.  Only the simulator stays out of scope.  There is no CPU path: without the HIP library
 these raise `NativeLibraryError`.
 """
 from __future__ import annotations
@@ -57,3 +61,36 @@ def task_space_terms(robot, q, vq, q_des, vq_des):
     row = lambda x: np.asarray(x, dtype=np.float64).reshape(1, -1)
     r = task_space_terms_batch(robot, row(q), row(vq), row(q_des), row(vq_des))
     return r["J_total"][0], r["J_dot_v"][0], r["e"][0], r["e_dot"][0]
+
+
+def dynamics_terms_batch(robot, q, vq=None, dtype="f64"):
+    """control.py:284-286 for B states at once -> dict of
+      M    [B,nq,nq]  robot.data.M after pin.computeAllTerms, both triangles filled
+      b    [B,nq]     pin.nonLinearEffects(model, data, q, vq)
+      g    [B,nq]     the gravity part of b (b at zero velocity)
+    from one launch of `ikg_dynamics_batch` (GPU) with the body inertias of the
+    robot's URDF (`ikgrasp.model.load_nextage_inertia`)."""
+    r = robot.solver.dynamics(q, vq, outputs=("M", "nle", "g"), dtype=dtype)
+    return {"M": r["M"], "b": r["nle"], "g": r["g"]}
+
+
+def control_torques_batch(robot, q, vq, q_des, vq_des, **gains):
+    """control.py:284-406 for B states at once (GPU, fp64) -> dict of
+      tau [B,nq], q_ddot_desired [B,nq], x_ddot_des_total [B,12], Lambda [B,2,6,6], f_c_total [B,12]
+    (f_c_total before the :375 bias, which enters tau only).  `gains`: Kp, Kv,
+    Kf, Kt, lambda_reg, qp_reg, fc_bias, zero_tau; defaults are the reference's."""
+    r = robot.solver.control_torques(q, vq, q_des, vq_des, **gains)
+    return {"tau": r["tau"], "q_ddot_desired": r["qdd"], "x_ddot_des_total": r["xdd"],
+            "Lambda": r["Lambda"].reshape(-1, 2, 6, 6), "f_c_total": r["fc"]}
+
+
+def controllaw(sim, robot, trajs, tcurrent, cube):
+    """Drop-in for the reference's `controllaw(sim, robot, trajs, tcurrent, cube)`
+    (control.py:242-410): reads the simulator state, evaluates the desired
+    trajectory at tcurrent, computes the torques in one B = 1 call of
+    `ikg_control_torque_batch` and steps the simulator with them."""
+    q, vq = sim.getpybulletstate()  # :254
+    row = lambda x: np.asarray(x, dtype=np.float64).reshape(1, -1)
+    q_des, vq_des = trajs[0](tcurrent), trajs[1](tcurrent)  # :269-270
+    tau = robot.solver.control_torques(row(q), row(vq), row(q_des), row(vq_des), outputs=("tau",))["tau"][0]
+    sim.step(tau.tolist())  # :410

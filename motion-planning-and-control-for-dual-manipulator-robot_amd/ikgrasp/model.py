@@ -133,6 +133,9 @@ class Frame:
 class KinematicTree:
     joints: list = field(default_factory=list)
     frames: dict = field(default_factory=dict)
+    # link name -> (mass, com xyz, inertial-frame rotation, 3x3 inertia about the com in the
+    # inertial frame): the raw <inertial> entries, expressed in the link frame (frames[link])
+    inertials: dict = field(default_factory=dict)
 
     @property
     def nq(self) -> int:
@@ -149,6 +152,17 @@ def parse_urdf(path_or_xml: str, base_placement=None) -> KinematicTree:
     else:
         root = ET.fromstring(path_or_xml)
     links = {l.get("name") for l in root.findall("link")}
+    inertials = {}
+    for l in root.findall("link"):
+        el = l.find("inertial")
+        if el is None:
+            continue
+        mass = float(el.find("mass").get("value")) if el.find("mass") is not None else 0.0
+        Ro, xyz = _origin(el)
+        it = el.find("inertia")
+        g = (lambda k: float(it.get(k, "0"))) if it is not None else (lambda k: 0.0)
+        I = np.array([[g("ixx"), g("ixy"), g("ixz")], [g("ixy"), g("iyy"), g("iyz")], [g("ixz"), g("iyz"), g("izz")]])
+        inertials[l.get("name")] = (mass, xyz, Ro, I)
     joints = {}
     children = {}
     child_links = set()
@@ -162,7 +176,7 @@ def parse_urdf(path_or_xml: str, base_placement=None) -> KinematicTree:
     roots = sorted(links - child_links)
     if len(roots) != 1:
         raise ValueError(f"URDF must have exactly one root link, found {roots}")
-    tree = KinematicTree()
+    tree = KinematicTree(inertials=inertials)
     identity = (np.eye(3), np.zeros(3))
     # the root link's body frame sits at the universe origin
     tree.frames[roots[0]] = Frame(roots[0], -1, np.eye(3), np.zeros(3))
@@ -325,7 +339,104 @@ class DualArmModel:
             Q=np.array(d["Q"]) if "Q" in d else None).validate()
 
 
+def _sym6(I: np.ndarray) -> np.ndarray:
+    return np.array([I[0, 0], I[0, 1], I[0, 2], I[1, 1], I[1, 2], I[2, 2]])
+
+
+def sym6_matrix(v) -> np.ndarray:
+    """(xx xy xz yy yz zz) -> symmetric 3x3."""
+    xx, xy, xz, yy, yz, zz = (float(x) for x in v)
+    return np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]])
+
+
+@dataclass
+class BodyInertias:
+    """Per joint (q order) the inertia of the body it moves, as Pinocchio's
+    URDF loader builds `model.inertias[1:]`: the joint's child link plus every
+    link reached from it through fixed joints (`appendBodyToJoint`: each link's
+    inertia transported by its fixed placement and summed); links fixed to the
+    universe are dropped.  Expressed in the canonical joint frame (module doc:
+    the Q_j^T change of joints with non-canonical axes).  Consumed by
+    `ikg_model_set_inertia` (include/ikgrasp.h)."""
+    mass: np.ndarray      # [nq]
+    com: np.ndarray       # [nq,3] centre of mass in the joint frame
+    inertia: np.ndarray   # [nq,6] xx xy xz yy yz zz about the com, joint-frame axes
+
+    @property
+    def nq(self) -> int:
+        return len(self.mass)
+
+    def matrices(self) -> np.ndarray:
+        return np.stack([sym6_matrix(v) for v in self.inertia]) if self.nq else np.zeros((0, 3, 3))
+
+    @staticmethod
+    def from_links(nq: int, links) -> "BodyInertias":
+        """Merge links = [(joint, mass, com [3], I_com [3,3])], all in their
+        joint's frame: total mass, mass-weighted centre, and the inertias
+        moved to that centre by the parallel-axis theorem."""
+        mass, com, inertia = np.zeros(nq), np.zeros((nq, 3)), np.zeros((nq, 6))
+        for j in range(nq):
+            mine = [(m, c, I) for (jj, m, c, I) in links if jj == j]
+            mt = sum(m for m, _, _ in mine)
+            if not mine or mt == 0.0:
+                continue
+            ct = sum(m * c for m, c, _ in mine) / mt
+            It = np.zeros((3, 3))
+            for m, c, I in mine:
+                d = c - ct
+                It += I + m * (float(d @ d) * np.eye(3) - np.outer(d, d))
+            mass[j], com[j], inertia[j] = mt, ct, _sym6(0.5 * (It + It.T))
+        return BodyInertias(mass, com, inertia)
+
+    @staticmethod
+    def from_tree(tree: KinematicTree) -> "BodyInertias":
+        links = []
+        for name, (m, xyz, Ro, I) in tree.inertials.items():
+            f = tree.frames[name]
+            if f.parent < 0:
+                continue  # fixed to the universe
+            R = f.R @ Ro
+            links.append((f.parent, m, f.R @ xyz + f.t, R @ I @ R.T))
+        return BodyInertias.from_links(tree.nq, links)
+
+    @staticmethod
+    def from_urdf(robot_urdf: str) -> "BodyInertias":
+        return BodyInertias.from_tree(parse_urdf(robot_urdf))
+
+    def validate(self, tol: float = 1e-12):
+        """mass >= 0; inertia about the com symmetric positive semi-definite
+        with principal moments obeying the triangle inequalities (a mass
+        distribution exists), each to `tol` relative to the largest moment."""
+        if self.com.shape != (self.nq, 3) or self.inertia.shape != (self.nq, 6):
+            raise ValueError("BodyInertias: com must be [nq,3] and inertia [nq,6]")
+        if not (np.all(np.isfinite(self.mass)) and np.all(np.isfinite(self.com)) and np.all(np.isfinite(self.inertia))):
+            raise ValueError("BodyInertias: non-finite entry")
+        for j in range(self.nq):
+            if self.mass[j] < 0:
+                raise ValueError(f"body {j}: negative mass")
+            w = np.linalg.eigvalsh(sym6_matrix(self.inertia[j]))
+            eps = tol * max(1.0, float(np.abs(w).max()))
+            if w[0] < -eps:
+                raise ValueError(f"body {j}: inertia is not positive semi-definite")
+            if w[2] > w[0] + w[1] + eps:
+                raise ValueError(f"body {j}: principal moments violate the triangle inequality")
+        return self
+
+    def to_json(self) -> str:
+        return json.dumps({"mass": self.mass.tolist(), "com": self.com.tolist(), "inertia": self.inertia.tolist()},
+                          indent=1)
+
+    @staticmethod
+    def from_json(text: str) -> "BodyInertias":
+        d = json.loads(text)
+        return BodyInertias(np.array(d["mass"], dtype=np.float64), np.array(d["com"], dtype=np.float64).reshape(-1, 3),
+                            np.array(d["inertia"], dtype=np.float64).reshape(-1, 6)).validate()
+
+
+GRAVITY = (0.0, 0.0, -9.81)  # Pinocchio's model.gravity and the simulator's (setup_pybullet.py:33), world frame
+
 DATA_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
+NEXTAGE_INERTIA_JSON = os.path.join(DATA_DIR, "nextage_inertia.json")
 NEXTAGE_JSON = os.path.join(DATA_DIR, "nextage_dualarm.json")
 
 
@@ -334,3 +445,10 @@ def load_nextage() -> DualArmModel:
     `tools/compile_model.py` from the reference URDFs)."""
     with open(NEXTAGE_JSON) as f:
         return DualArmModel.from_json(f.read())
+
+
+def load_nextage_inertia() -> BodyInertias:
+    """The Nextage body inertias (compiled by `tools/compile_model.py` from the
+    reference URDF's <inertial> entries)."""
+    with open(NEXTAGE_INERTIA_JSON) as f:
+        return BodyInertias.from_json(f.read())

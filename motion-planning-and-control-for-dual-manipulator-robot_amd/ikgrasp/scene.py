@@ -30,6 +30,7 @@ class Robot:
         """scene: a CollisionScene, "nextage" (the reference scene compiled by
         tools/compile_model.py, only valid with the default model) or None."""
         self.ik_model = model if model is not None else load_nextage()
+        self._default_model = model is None
         self.model = _ModelView(self.ik_model)
         self.q0 = np.zeros(self.model.nq)
         self.device = device
@@ -48,6 +49,9 @@ class Robot:
         if self._solver is None:
             from .solver import IKSolver
             self._solver = IKSolver(self.ik_model, device=self.device, scene=self.scene)
+            if self._default_model:  # the shipped Nextage tables come with the URDF's body inertias
+                from .model import load_nextage_inertia
+                self._solver.set_inertia(load_nextage_inertia())
         return self._solver
 
 

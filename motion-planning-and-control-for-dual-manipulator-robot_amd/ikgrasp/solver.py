@@ -14,7 +14,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .model import DualArmModel, load_nextage
+from .model import GRAVITY, DualArmModel, load_nextage, load_nextage_inertia
 
 _DT = {"f64": (_lib.IKG_F64, np.float64), "f32": (_lib.IKG_F32, np.float32)}
 
@@ -84,6 +84,9 @@ class IKSolver:
         self.scene = None
         if scene is not None:
             self.set_collision(scene)
+        self.inertias = None
+        if model is None:  # the shipped Nextage tables come with the URDF's body inertias
+            self.set_inertia(load_nextage_inertia())
 
     def set_collision(self, scene):
         """Attach the collision scene (ikg_model_set_collision); enables
@@ -91,6 +94,17 @@ class IKSolver:
         self._cdesc = _lib.collision_desc(scene)
         _lib.check(self.lib.ikg_model_set_collision(self._h, C.byref(self._cdesc)))
         self.scene = scene
+
+    def set_inertia(self, inertias, gravity=GRAVITY):
+        """Attach the body inertias (ikgrasp.model.BodyInertias, one per joint
+        in q order) and the world-frame gravity (ikg_model_set_inertia);
+        enables `dynamics()`."""
+        if inertias.nq != self.nq:
+            raise ValueError(f"inertias describe {inertias.nq} bodies, the model has {self.nq} joints")
+        self._idesc = _lib.inertia_desc(inertias, gravity)
+        _lib.check(self.lib.ikg_model_set_inertia(self._h, C.byref(self._idesc)))
+        self.inertias = inertias
+        self.gravity = tuple(float(x) for x in gravity)
 
     def _auto_specialize(self, device, code):
         if self._specialize is False or (device, code) in self._specialized:
@@ -376,4 +390,94 @@ class IKSolver:
         _lib.check(self.lib.ikg_frame_kinematics_batch(
             self._h, self.device, code, ptr(qq), ptr(vv), ptr(qd), ptr(vd), B, int(rf), C.byref(out), None,
             _lib.IKG_FLAG_HOST_POINTERS))
+        return res
+
+    # ------------------------------------------------------------------ controller dynamics (control.py:284-286)
+    DYNAMICS_OUTPUTS = ("M", "nle", "g")
+
+    def dynamics(self, q, v=None, outputs=("M", "nle"), dtype="f64", stream=None) -> dict:
+        """ikg_dynamics_batch: per state the joint-space inertia matrix
+        M [B,nq,nq] (data.M of pin.computeAllTerms, both triangles), the
+        non-linear effects nle [B,nq] (pin.nonLinearEffects) and g [B,nq] (nle
+        at zero velocity).  q, v [B,nq] (numpy, or torch tensors on a ROCm
+        device); v None = zero velocity.  Needs `set_inertia`."""
+        unknown = set(outputs) - set(self.DYNAMICS_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        nq = self.nq
+        shapes = {"M": (nq, nq), "nle": (nq,), "g": (nq,)}
+        if _is_torch(q):
+            import torch
+            code, _ = _dtype(q.dtype)
+            dev = q.device
+            if not q.is_cuda:
+                raise ValueError("torch inputs must live on a ROCm device (or pass numpy arrays)")
+            prep = lambda x: None if x is None else x.to(device=dev, dtype=q.dtype).contiguous().view(-1, nq)
+            qq, vv = prep(q), prep(v)
+            B = qq.shape[0]
+            if vv is not None and vv.shape[0] != B:
+                raise ValueError(f"v has {vv.shape[0]} rows, q has {B}")
+            res = {k: torch.empty((B,) + shapes[k], dtype=q.dtype, device=dev) for k in outputs}
+            ptr = lambda x: None if x is None else x.data_ptr()
+            out = _lib.DynamicsOut(*[ptr(res.get(k)) for k in self.DYNAMICS_OUTPUTS])
+            s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(self.lib.ikg_dynamics_batch(self._h, dev.index or 0, code, ptr(qq), ptr(vv), B, C.byref(out),
+                                                   C.c_void_p(s), 0))
+            return res
+        code, npt = _dtype(dtype)
+        prep = lambda x: None if x is None else np.ascontiguousarray(x, dtype=npt).reshape(-1, nq)
+        qq, vv = prep(q), prep(v)
+        B = qq.shape[0]
+        if vv is not None and vv.shape[0] != B:
+            raise ValueError(f"v has {vv.shape[0]} rows, q has {B}")
+        res = {k: np.empty((B,) + shapes[k], dtype=npt) for k in outputs}
+        ptr = lambda x: None if x is None else x.ctypes.data
+        out = _lib.DynamicsOut(*[ptr(res.get(k)) for k in self.DYNAMICS_OUTPUTS])
+        _lib.check(self.lib.ikg_dynamics_batch(self._h, self.device, code, ptr(qq), ptr(vv), B, C.byref(out), None,
+                                               _lib.IKG_FLAG_HOST_POINTERS))
+        return res
+
+    # ------------------------------------------------------------------ controller torques (control.py:284-406)
+    CONTROL_OUTPUTS = ("tau", "qdd", "xdd", "Lambda", "fc")
+
+    def control_torques(self, q, v, q_des, v_des, outputs=CONTROL_OUTPUTS, stream=None, **gains) -> dict:
+        """ikg_control_torque_batch (fp64): per state the controller's torques
+        tau [B,nq] (what sim.step receives), the QP's solution qdd [B,nq],
+        xdd [B,12] (x_ddot_des_total), Lambda [B,2,36] and fc [B,12] (before the
+        bias).  q, v, q_des, v_des [B,nq] (numpy, or float64 torch tensors on a
+        ROCm device; v / v_des None = zero).  `gains`: Kp, Kv, Kf, Kt,
+        lambda_reg, qp_reg, fc_bias, zero_tau (defaults: the reference's)."""
+        unknown = set(outputs) - set(self.CONTROL_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        nq = self.nq
+        prm = _lib.control_params(**gains)
+        shapes = {"tau": (nq,), "qdd": (nq,), "xdd": (12,), "Lambda": (2, 36), "fc": (12,)}
+        if _is_torch(q):
+            import torch
+            if not q.is_cuda or q.dtype != torch.float64:
+                raise ValueError("torch inputs must be float64 tensors on a ROCm device (or pass numpy arrays)")
+            dev = q.device
+            prep = lambda x: None if x is None else x.to(device=dev, dtype=torch.float64).contiguous().view(-1, nq)
+            arrs = [prep(x) for x in (q, v, q_des, v_des)]
+            empty = lambda B, k: torch.empty((B,) + shapes[k], dtype=torch.float64, device=dev)
+            ptr = lambda x: None if x is None else x.data_ptr()
+            s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+            device, flags = dev.index or 0, 0
+        else:
+            prep = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.float64).reshape(-1, nq)
+            arrs = [prep(x) for x in (q, v, q_des, v_des)]
+            empty = lambda B, k: np.empty((B,) + shapes[k], dtype=np.float64)
+            ptr = lambda x: None if x is None else x.ctypes.data
+            s, device, flags = None, self.device, _lib.IKG_FLAG_HOST_POINTERS
+        if arrs[2] is None:
+            raise ValueError("q_des is required")
+        B = arrs[0].shape[0]
+        for name, x in zip(("v", "q_des", "v_des"), arrs[1:]):
+            if x is not None and x.shape[0] != B:
+                raise ValueError(f"{name} has {x.shape[0]} rows, q has {B}")
+        res = {k: empty(B, k) for k in outputs}
+        out = _lib.ControlOut(*[ptr(res.get(k)) for k in self.CONTROL_OUTPUTS])
+        _lib.check(self.lib.ikg_control_torque_batch(self._h, device, *[ptr(x) for x in arrs], B, C.byref(prm),
+                                                     C.byref(out), s, flags))
         return res
