@@ -256,6 +256,23 @@ extern "C" int ikg_emu_solve(const ikg_model_desc* d, int dtype, const void* tar
   return chest_mismatch ? -3 : 0;
 }
 
+// Which tables and specialisation a model gets (tests/test_robot_family.py):
+// build_kmodel<double> and choose_spec, read-only.  out = spec, wrist,
+// hand_axis, rot_mask, zmask, pattern, n_passive, nq.
+extern "C" int ikg_emu_model_info(const ikg_model_desc* d, int32_t out[8]) {
+  static thread_local ikg::KModel<double> m;
+  ikg::build_kmodel<double>(*d, m);
+  out[0] = ikg::choose_spec(m);
+  out[1] = m.wrist;
+  out[2] = m.hand_axis;
+  out[3] = m.rot_mask;
+  out[4] = m.zmask;
+  out[5] = m.pattern;
+  out[6] = m.n_passive;
+  out[7] = m.nq;
+  return 0;
+}
+
 template <typename T>
 void emu_col(const ikg_model_desc* d, const ikg_collision_desc* cd, const void* q, const void* targets, int64_t B,
              uint8_t* out) {

@@ -145,9 +145,21 @@ def cube_hooks(cube_urdf, hooks=("LARM_HOOK", "RARM_HOOK")):
     return [c.frames[h][1] for h in hooks]
 
 
+def damped_step(lam):
+    """J^T (J J^T + lam I)^-1 e: ik_oracle.computeqgrasppose's `lam > 0` step."""
+    return lambda J, e: J.T @ np.linalg.solve(J @ J.T + lam * np.eye(len(e)), e)
+
+
+def lstsq_step(J, e):
+    """The minimum-norm least-squares step by LAPACK's gelsd instead of pinv's SVD product."""
+    return np.linalg.lstsq(J, e, rcond=None)[0]
+
+
 def computeqgrasppose(model, hooks, q0, cube_R, cube_t, hands=("LARM_EFF", "RARM_EFF"), max_iters=ik.MAX_ITERS,
-                      dt=ik.DT, eps=ik.EPSILON):
+                      dt=ik.DT, eps=ik.EPSILON, step=None):
     """inverse_geometry.py:41-100 on a generic model (no collision term).
+    `step(J, e)` replaces np.linalg.pinv(J) @ e (np.linalg.lstsq for the
+    rounding check of the family fixtures; `damped_step(lam)`).
     Returns (q, converged, updates, (|eL|, |eR|))."""
     cube = (np.asarray(cube_R, dtype=np.float64), np.asarray(cube_t, dtype=np.float64))
     targets = [ik.se3_mul(cube, hk) for hk in hooks]
@@ -164,7 +176,8 @@ def computeqgrasppose(model, hooks, q0, cube_R, cube_t, hands=("LARM_EFF", "RARM
         if nL < eps and nR < eps:
             return q, True, it, (nL, nR)
         J = np.vstack([model.frame_jacobian_local(q, h, oMi) for h in hands])
-        vq = np.linalg.pinv(J) @ np.hstack([eL, eR])
+        e = np.hstack([eL, eR])
+        vq = step(J, e) if step is not None else np.linalg.pinv(J) @ e
         q = np.minimum(np.maximum(model.lower, q + vq * dt), model.upper)
     _, (eL, eR) = errors(q)
     return q, False, max_iters, (np.linalg.norm(eL), np.linalg.norm(eR))

@@ -64,6 +64,10 @@
    World-fixed palettes for the synthetic scenes of the GPU leg, and one
    scene of geometries attached to Nextage joints at seeded q (world
    placements from the collision oracle's FK).
+
+Generators of their own: `make_dynamics_golden.py` (dynamics_cases.npz) and
+`make_family_golden.py` (the robot family of tests/robot_family.py:
+family/<member>.urdf, <member>_cube.urdf and family_cases.npz).
 """
 import json
 import os
