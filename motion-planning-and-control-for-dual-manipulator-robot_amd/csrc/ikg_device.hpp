@@ -870,7 +870,8 @@ IKG_HD inline void log6_iter(const T* R, const T* p, T* e, ThetaTrack<T>* tk = n
 // sin/cos of every supporting joint are carried across iterations: after an
 // update q -> q + d the pair is advanced by the angle-addition formula with
 // Taylor series of sin d / cos d (|d| <= kIncMax keeps the truncation below
-// 1e-18 in fp64), and recomputed exactly every kResync iterations, after a
+// 1e-18 in fp64; the fp64 short step: the same rotation as three in-place
+// shears), and recomputed exactly every kResync iterations, after a
 // large step, or after a clamp.  This replaces 7 sincos calls per lane and
 // iteration of pin.framesForwardKinematics (inverse_geometry.py:58).
 template <typename T>
@@ -911,7 +912,26 @@ struct Trig<double> {
     c = c * cd - s * sd;
     s = sn;
   }
+  // The short step rotates (c, s) by d as three shears, in place:
+  //   c -= t s;  s += sd c;  c -= t s,   t = tan(d / 2), sd = sin d.
+  // No shear needs the old and the new value of s or c at once, so the update
+  // keeps no copy of the old pair (the angle-addition form cost the pair
+  // kernel 7 register copies per update).  |d| <= 0.025: the
+  // first dropped term of t is 62 d^9 / 1,451,520 < 2e-19 absolute and that of
+  // sd is d^9/9! < 2e-20, both well under an ulp of s and c; each shear has
+  // determinant 1, so s^2 + c^2 is kept to rounding whatever the truncation.
   IKG_HD static inline void step(double d, double& s, double& c) {
+    const double d2 = d * d;
+    const double sd = d + d * d2 * (-1.0 / 6 + d2 * (1.0 / 120 + d2 * (-1.0 / 5040)));
+    const double t = d * (0.5 + d2 * (1.0 / 24 + d2 * (1.0 / 240 + d2 * (17.0 / 40320))));
+    c = fma(-t, s, c);
+    s = fma(sd, c, s);
+    c = fma(-t, s, c);
+  }
+  // the angle-addition form the short step had before (cos d by its own
+  // series): kept for the host test that measures the shear form against it
+  // (tests/test_trig_step.py), not called by any kernel
+  IKG_HD static inline void step_addition(double d, double& s, double& c) {
     const double d2 = d * d;
     const double sd = d + d * d2 * (-1.0 / 6 + d2 * (1.0 / 120 + d2 * (-1.0 / 5040)));
     const double cd = 1.0 + d2 * (-0.5 + d2 * (1.0 / 24 + d2 * (-1.0 / 720)));

@@ -390,7 +390,11 @@ extern "C" int ikg_emu_pairs(int dtype, int64_t n, const int32_t* kindA, const d
 // The loop's math helpers over arrays (tests/test_host_emu.py accuracy checks):
 // fn 0: cw_sincos (fp64), 1: cw_sincos (fp32), 2: the packed pair's sincos
 // (both halves), 3: atan2_upper (fp32), 4: atan2_upper (packed pair).
-// out holds 2 values per input (sin, cos) for fn 0-2, 1 for fn 3-4.
+// fn 5: Trig<double>::step, fn 6: the angle-addition form it replaced
+// (step_addition): from the exact (sin, cos) of the angle y, Trig<double>::kResync
+// consecutive steps of x with no resync (tests/test_trig_step.py).
+// out holds 2 values per input (sin, cos) for fn 0-2, 1 for fn 3-4, 4 for fn
+// 5-6 (the starting pair, then the pair after the steps).
 extern "C" int ikg_emu_math(int fn, int64_t n, const double* x, const double* y, double* out) {
   using namespace ikg;
   for (int64_t i = 0; i < n; ++i) {
@@ -416,6 +420,21 @@ extern "C" int ikg_emu_math(int fn, int64_t n, const double* x, const double* y,
         const v2f r = atan2_upper(v2f{(float)y[i], (float)y[i]}, v2f{(float)x[i], (float)x[i]});
         if (r.x != r.y) return -2;
         out[i] = r.x;
+        break;
+      }
+      case 5:
+      case 6: {
+        double s = std::sin(y[i]), c = std::cos(y[i]);
+        out[4 * i] = s;
+        out[4 * i + 1] = c;
+        for (int k = 0; k < Trig<double>::kResync; ++k) {
+          if (fn == 5)
+            Trig<double>::step(x[i], s, c);
+          else
+            Trig<double>::step_addition(x[i], s, c);
+        }
+        out[4 * i + 2] = s;
+        out[4 * i + 3] = c;
         break;
       }
       default: return -1;
