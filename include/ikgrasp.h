@@ -422,6 +422,95 @@ int ikg_control_torque_batch(const ikg_model* model, int device, const void* q, 
                              const void* v_des, int64_t B, const ikg_control_params* params,
                              const ikg_control_out* out, void* stream, uint32_t flags);
 
+/*
+ * Forward dynamics: qdd = M(q)^-1 (tau - nle(q, v)), i.e. pin.aba(model, data,
+ * q, v, tau), for a batch of states (fp64).  The dynamics kernel writes nle to
+ * device scratch from the model's workspace pool (65,536 states per pass); a
+ * second kernel forms M in LDS, each row about its own joint's origin so that
+ * the small rows keep their relative accuracy under the division, factors
+ * M = L D L^T and substitutes.
+ *   q, v, tau [B,nq] (v NULL = zero velocity);  qdd [B,nq].
+ * Needs ikg_model_set_inertia (else IKG_EINVAL).  Host-pointer calls check the
+ * inputs for finiteness.  B == 0 is a no-op.  Stream-ordered and capturable
+ * like ikg_control_torque_batch.
+ */
+int ikg_forward_dynamics_batch(const ikg_model* model, int device, const void* q, const void* v, const void* tau,
+                               int64_t B, void* qdd, void* stream, uint32_t flags);
+
+/*
+ * A Bezier curve with the semantics of the reference's Bezier.__call__ /
+ * eval_horner (control.py:30-46): out[k] = curve(times[k]) for K times (fp64).
+ *   points [n_points, dim] is always a HOST array (it travels as kernel
+ *   arguments); times [K] and out [K, dim] are device arrays, or host arrays
+ *   with IKG_FLAG_HOST_POINTERS.
+ * A curve of two control points returns mult * P0 whatever the time, as the
+ * reference does.  n_points < 2, n_points > 64, dim outside [1, IKG_MAX_NQ] or
+ * t_max <= t_min return IKG_EINVAL.  With host pointers a time outside
+ * [t_min, t_max] returns IKG_EINVAL (the reference raises there); device-pointer
+ * callers keep their times in range.  K == 0 is a no-op.
+ */
+int ikg_bezier_eval_batch(int device, const double* points, int32_t n_points, int32_t dim, double t_min, double t_max,
+                          double mult, const void* times, int64_t K, void* out, void* stream, uint32_t flags);
+
+/*
+ * Closed-loop rollout: B copies of the reference's demo loop (control.py:461-463)
+ * with a rigid-body plant in place of the simulator, `ticks` ticks in one call
+ * and no host round trip between them.  A tick k of a state (q, v, t):
+ *   1. q_des = Bq(clamp(t)), v_des = Bv(clamp(t)): each curve evaluated at t
+ *      clamped to its own [t_min, t_max] (the reference's loop never leaves the
+ *      range; clamping holds the end point)
+ *   2. tau = the torque law of ikg_control_torque_batch (control.py:284-406)
+ *   3. qdd = M^-1 (tau - nle)
+ *   4. v += dt_sim qdd, then q += dt_sim v   (semi-implicit Euler, Bullet's scheme)
+ *   5. t += dt_traj                          (one fp64 add, as `tcur += DT`)
+ * dt_traj defaults to 1e-2 with dt_sim = 1e-3 (config.py:21): the reference
+ * advances its trajectory clock by DT = 0.01 per 1 ms simulator tick
+ * (control.py:449, :463), and the default keeps that.
+ * THE PLANT is the free rigid-body tree of ikg_model_set_inertia: no contact, no
+ * cube, no joint limits and no joint damping.  The default fc_bias (-200 N,
+ * control.py:375) therefore has nothing to push against here: it accelerates
+ * the arms; pass fc_bias = 0 for a free-space tracking run.
+ * Per tick three kernels run (frame kinematics, dynamics, step); batches above
+ * 65,536 states run chunk by chunk, all ticks of a chunk before the next chunk.
+ *   q0, v0 [B,nq] (v0 NULL = zero) are never written and must not overlap the
+ *   outputs; t0 [B] or NULL = the q curve's t_min.  q_curve and v_curve have
+ *   dim = nq (ikg_bezier.points is a host array whatever the flags); a curve of
+ *   a derivative carries its own mult (Bezier.derivative: mult / (t_max - t_min)).
+ *   Outputs, all optional: the final q, v [B,nq] and t [B]; with record_every > 0
+ *   q_hist, v_hist, tau_hist [B,R,nq], R = ticks / record_every: record j is
+ *   the state after tick (j + 1) record_every - 1 and the tau applied in that tick.
+ * fp64 only, like the torque law.  Needs ikg_model_set_inertia.  Host-pointer
+ * calls check q0, v0, t0 for finiteness.  B == 0 is a no-op.  Stream-ordered and
+ * capturable with device pointers (scratch: "Graphs" above).
+ */
+typedef struct ikg_bezier {
+  const double* points; /* host, [n_points, nq] */
+  int32_t n_points;     /* 2 .. 64 */
+  double t_min, t_max;
+  double mult;
+} ikg_bezier;
+
+typedef struct ikg_rollout_params {
+  ikg_control_params control;
+  double dt_sim;        /* 1e-3 */
+  double dt_traj;       /* 1e-2 */
+  int32_t ticks;        /* >= 0 */
+  int32_t record_every; /* 0 = no history */
+} ikg_rollout_params;
+void ikg_rollout_params_default(ikg_rollout_params* p);
+
+typedef struct ikg_rollout_out {
+  void* q;
+  void* v;
+  void* t;
+  void* q_hist;
+  void* v_hist;
+  void* tau_hist;
+} ikg_rollout_out;
+int ikg_control_rollout(const ikg_model* model, int device, const void* q0, const void* v0, const void* t0, int64_t B,
+                        const ikg_bezier* q_curve, const ikg_bezier* v_curve, const ikg_rollout_params* params,
+                        const ikg_rollout_out* out, void* stream, uint32_t flags);
+
 /* Thread-local message of the last failure ("" if none). */
 const char* ikg_last_error(void);
 

@@ -1267,6 +1267,301 @@ int ikg_control_torque_batch(const ikg_model* model, int device, const void* q, 
 
 }  // extern "C"
 
+// ------------------------------------------------------------ forward dynamics, Bezier curves, closed-loop rollout
+namespace {
+
+int forward_dynamics(ikg_model* model, int device, const void* q, const void* v, const void* tau, int64_t B,
+                     void* qdd, hipStream_t s, uint32_t flags) {
+  using T = double;
+  if (!ikg::stream_capturing(s)) ikg::ws_drain(&model->ws);
+  const ikg::KModel<T>* dm = nullptr;
+  int rc = model->device_tables<T>(device, &dm);
+  if (rc) return rc;
+  const ikg::KInertia<T>* di = nullptr;
+  if ((rc = model->inertia_tables<T>(device, &di))) return rc;
+  const int nq = model->desc.nq;
+  Staging st(s);
+  const bool host = flags & IKG_FLAG_HOST_POINTERS;
+  const void *dq = q, *dv = v, *dtau = tau;
+  void* dout = qdd;
+  if (host) {
+    dq = st.in(q, sizeof(T) * nq * B);
+    dv = st.in(v, sizeof(T) * nq * B);
+    dtau = st.in(tau, sizeof(T) * nq * B);
+    dout = st.out(sizeof(T) * nq * B);
+  }
+  if (st.rc) return st.rc;
+  const int64_t chunk = std::min(B, kCtlChunk);
+  const size_t per = (size_t)nq;  // nle
+  void* ws = nullptr;
+  hipError_t e = ikg::ws_alloc(&model->ws, &ws, sizeof(T) * per * chunk, s);
+  if (e != hipSuccess) return fail(IKG_ENOMEM, "forward dynamics scratch (%zu bytes): %s", sizeof(T) * per * chunk,
+                                   hipGetErrorString(e));
+  ikg::poison_float(ws, sizeof(T) * per * chunk, s);
+  T* wn = (T*)ws;
+  const char* what = "";
+  for (int64_t off = 0; off < B && e == hipSuccess; off += chunk) {
+    const int64_t n = std::min(chunk, B - off);
+    auto at = [&](const void* p) { return p ? (const void*)((const T*)p + (size_t)nq * off) : nullptr; };
+    what = "ikg dynamics kernel launch";
+    e = ikg::launch_dynamics<T>(dm, di, nq, at(dq), at(dv), n, ikg::DynOut{nullptr, wn, nullptr}, s);
+    if (e != hipSuccess) break;
+    what = "ikg forward dynamics kernel launch";
+    e = ikg::launch_forward_dynamics(dm, di, nq, at(dq), wn, at(dtau), n, (T*)dout + (size_t)nq * off, s);
+  }
+  const hipError_t ef = ikg::ws_free(&model->ws, ws, s);
+  if (e != hipSuccess) return hip_fail(e, what);
+  if (ef != hipSuccess) return hip_fail(ef, "forward dynamics scratch free");
+  if (host) {
+    st.back(qdd, dout, sizeof(T) * nq * B);
+    if (st.rc) return st.rc;
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+  }
+  return IKG_OK;
+}
+
+int check_bezier(const ikg_bezier* c, int dim, const char* what) {
+  if (!c || !c->points) return fail(IKG_EINVAL, "%s: curve or its points are NULL", what);
+  if (c->n_points < 2) return fail(IKG_EINVAL, "%s: a curve needs at least 2 control points", what);
+  if (c->n_points > ikg::kMaxBezier)
+    return fail(IKG_EINVAL, "%s: %d control points (max %d)", what, c->n_points, ikg::kMaxBezier);
+  if (!std::isfinite(c->t_min) || !std::isfinite(c->t_max) || !(c->t_max > c->t_min))
+    return fail(IKG_EINVAL, "%s: t_max must be above t_min", what);
+  if (!std::isfinite(c->mult)) return fail(IKG_EINVAL, "%s: mult is not finite", what);
+  return check_finite<double>(c->points, (int64_t)c->n_points * dim, what);
+}
+
+// [P (n x dim)] [bc (n)] of one curve
+void append_curve(std::vector<double>& tab, const ikg_bezier& c, int dim) {
+  tab.insert(tab.end(), c.points, c.points + (size_t)c.n_points * dim);
+  double bc[ikg::kMaxBezier];
+  ikg::bezier_coeffs(c.n_points, bc);
+  tab.insert(tab.end(), bc, bc + c.n_points);
+}
+
+int control_rollout(ikg_model* model, int device, const void* q0, const void* v0, const void* t0, int64_t B,
+                    const ikg_bezier& bq, const ikg_bezier& bv, const ikg_rollout_params& params,
+                    const ikg_rollout_out& out, hipStream_t s, uint32_t flags) {
+  using T = double;
+  if (!ikg::stream_capturing(s)) ikg::ws_drain(&model->ws);
+  const ikg::KModel<T>* dm = nullptr;
+  int rc = model->device_tables<T>(device, &dm);
+  if (rc) return rc;
+  const ikg::KInertia<T>* di = nullptr;
+  if ((rc = model->inertia_tables<T>(device, &di))) return rc;
+  const int nq = model->desc.nq;
+  const int64_t ticks = params.ticks, every = params.record_every;
+  const int64_t R = every > 0 ? ticks / every : 0;
+  const size_t sz[6] = {(size_t)nq, (size_t)nq, 1, (size_t)(R * nq), (size_t)(R * nq), (size_t)(R * nq)};  // per state
+  void* host_out[6] = {out.q, out.v, out.t, R ? out.q_hist : nullptr, R ? out.v_hist : nullptr,
+                       R ? out.tau_hist : nullptr};
+  void* dev_out[6];
+  Staging st(s);
+  const bool host = flags & IKG_FLAG_HOST_POINTERS;
+  const void *dq0 = q0, *dv0 = v0, *dt0 = t0;
+  if (host) {
+    dq0 = st.in(q0, sizeof(T) * nq * B);
+    dv0 = st.in(v0, sizeof(T) * nq * B);
+    dt0 = st.in(t0, sizeof(T) * B);
+  }
+  for (int i = 0; i < 6; ++i) dev_out[i] = host && host_out[i] ? st.out(sizeof(T) * sz[i] * B) : host_out[i];
+  if (st.rc) return st.rc;
+  std::vector<double> tab;
+  append_curve(tab, bq, nq);
+  append_curve(tab, bv, nq);
+  // scratch: the torque law's (M, J, nle, dJ v, e, e'), the desired state, the
+  // state rows the caller did not ask for, and the curve table
+  const int64_t chunk = std::min(B, kCtlChunk);
+  const size_t per = (size_t)nq * nq + 12 * (size_t)nq + nq + 36 + 2 * (size_t)nq + (dev_out[0] ? 0 : nq) +
+                     (dev_out[1] ? 0 : nq) + (dev_out[2] ? 0 : 1);
+  const size_t bytes = sizeof(T) * (per * chunk + tab.size());
+  void* ws = nullptr;
+  hipError_t e = ikg::ws_alloc(&model->ws, &ws, bytes, s);
+  if (e != hipSuccess) return fail(IKG_ENOMEM, "rollout scratch (%zu bytes): %s", bytes, hipGetErrorString(e));
+  ikg::poison_float(ws, bytes, s);
+  T* wM = (T*)ws;
+  T* wJ = wM + (size_t)nq * nq * chunk;
+  T* wn = wJ + 12 * (size_t)nq * chunk;
+  T* wdJv = wn + (size_t)nq * chunk;
+  T* werr = wdJv + 12 * chunk;
+  T* wderr = werr + 12 * chunk;
+  T* wqd = wderr + 12 * chunk;
+  T* wvd = wqd + (size_t)nq * chunk;
+  T* next = wvd + (size_t)nq * chunk;
+  T* sq = nullptr;
+  T* sv = nullptr;
+  T* stt = nullptr;
+  if (!dev_out[0]) sq = next, next += (size_t)nq * chunk;
+  if (!dev_out[1]) sv = next, next += (size_t)nq * chunk;
+  if (!dev_out[2]) stt = next, next += chunk;
+  T* wtab = next;
+  const ikg::KCtl<T> prm = ikg::make_kctl<T>(params.control);
+  const char* what = "rollout curve table upload";
+  e = ikg::launch_table_write(wtab, tab.data(), tab.size(), s);
+  for (int64_t off = 0; off < B && e == hipSuccess; off += chunk) {
+    const int64_t n = std::min(chunk, B - off);
+    auto at = [&](const void* p, size_t w) { return p ? (const void*)((const T*)p + w * off) : nullptr; };
+    auto ao = [&](void* p, size_t w) { return p ? (void*)((T*)p + w * off) : nullptr; };
+    ikg::StepArgs a;
+    a.q = dev_out[0] ? ao(dev_out[0], sz[0]) : sq;
+    a.v = dev_out[1] ? ao(dev_out[1], sz[1]) : sv;
+    a.t = dev_out[2] ? ao(dev_out[2], sz[2]) : stt;
+    a.qdes = wqd;
+    a.vdes = wvd;
+    a.cv = ikg::RolloutCurves{wtab, bq.n_points, bv.n_points, bq.t_min, bq.t_max, bq.mult, bv.t_min, bv.t_max, bv.mult};
+    a.dt_sim = params.dt_sim;
+    a.dt_traj = params.dt_traj;
+    a.q_hist = ao(dev_out[3], sz[3]);
+    a.v_hist = ao(dev_out[4], sz[4]);
+    a.tau_hist = ao(dev_out[5], sz[5]);
+    a.R = R;
+    a.slot = -1;
+    what = "ikg rollout init kernel launch";
+    e = ikg::launch_rollout_init(at(dq0, nq), at(dv0, nq), at(dt0, 1), nq, n, a, s);
+    for (int64_t k = 0; k < ticks && e == hipSuccess; ++k) {
+      const ikg::FrameKinOut fo{nullptr, nullptr, wJ, nullptr, wdJv, werr, wderr};
+      what = "ikg frame kinematics kernel launch";
+      e = ikg::launch_frame_kin<T>(dm, nq, model->spec, a.q, a.v, wqd, wvd, n, IKG_LOCAL_WORLD_ALIGNED, fo, s);
+      if (e != hipSuccess) break;
+      what = "ikg dynamics kernel launch";
+      e = ikg::launch_dynamics<T>(dm, di, nq, a.q, a.v, n, ikg::DynOut{wM, wn, nullptr}, s);
+      if (e != hipSuccess) break;
+      what = "ikg control step kernel launch";
+      a.slot = (R && (k + 1) % every == 0 && (k + 1) / every <= R) ? (k + 1) / every - 1 : -1;
+      e = ikg::launch_control_step(ikg::CtlIn{wM, wn, wJ, wdJv, werr, wderr}, nq, n, prm, a, s);
+    }
+  }
+  const hipError_t ef = ikg::ws_free(&model->ws, ws, s);
+  if (e != hipSuccess) return hip_fail(e, what);
+  if (ef != hipSuccess) return hip_fail(ef, "rollout scratch free");
+  if (host) {
+    for (int i = 0; i < 6; ++i)
+      if (host_out[i]) st.back(host_out[i], dev_out[i], sizeof(T) * sz[i] * B);
+    if (st.rc) return st.rc;
+    e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+  }
+  return IKG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ikg_forward_dynamics_batch(const ikg_model* model, int device, const void* q, const void* v, const void* tau,
+                               int64_t B, void* qdd, void* stream, uint32_t flags) {
+  g_err[0] = 0;
+  if (!model) return fail(IKG_EINVAL, "model is NULL");
+  if (B < 0) return fail(IKG_EINVAL, "B must be >= 0");
+  if (B > 0 && (!q || !tau || !qdd)) return fail(IKG_EINVAL, "q, tau and qdd are required");
+  if (B > (int64_t)1 << 40) return fail(IKG_EINVAL, "B too large");
+  if (!model->has_inertia) return fail(IKG_EINVAL, "no body inertias attached (ikg_model_set_inertia)");
+  if (flags & IKG_FLAG_HOST_POINTERS) {  // the device code is built with -ffinite-math-only
+    const int64_t n = B * model->desc.nq;
+    int rc = check_finite<double>(q, n, "q");
+    if (!rc && v) rc = check_finite<double>(v, n, "v");
+    if (!rc) rc = check_finite<double>(tau, n, "tau");
+    if (rc) return rc;
+  }
+  DeviceGuard g(device);
+  if (g.rc) return g.rc;
+  if (B == 0) return IKG_OK;
+  return forward_dynamics(const_cast<ikg_model*>(model), device, q, v, tau, B, qdd, (hipStream_t)stream, flags);
+}
+
+int ikg_bezier_eval_batch(int device, const double* points, int32_t n_points, int32_t dim, double t_min, double t_max,
+                          double mult, const void* times, int64_t K, void* out, void* stream, uint32_t flags) {
+  g_err[0] = 0;
+  if (dim < 1 || dim > IKG_MAX_NQ) return fail(IKG_EINVAL, "dim must be in [1, %d]", IKG_MAX_NQ);
+  const ikg_bezier c{points, n_points, t_min, t_max, mult};
+  int rc = check_bezier(&c, dim, "points");
+  if (rc) return rc;
+  if (K < 0) return fail(IKG_EINVAL, "K must be >= 0");
+  if (K > 0 && (!times || !out)) return fail(IKG_EINVAL, "times and out are required");
+  if (K > (int64_t)1 << 40) return fail(IKG_EINVAL, "K too large");
+  const bool host = flags & IKG_FLAG_HOST_POINTERS;
+  if (host) {
+    const double* t = (const double*)times;
+    for (int64_t k = 0; k < K; ++k)
+      if (!(t[k] >= t_min && t[k] <= t_max))
+        return fail(IKG_EINVAL, "times[%lld] = %g is outside [%g, %g]", (long long)k, t[k], t_min, t_max);
+  }
+  DeviceGuard g(device);
+  if (g.rc) return g.rc;
+  if (K == 0) return IKG_OK;
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<double> tab;
+  append_curve(tab, c, dim);
+  Staging st(s);
+  double* dtab = (double*)st.in_alloc(sizeof(double) * tab.size());
+  const void* dt = host ? st.in(times, sizeof(double) * K) : times;
+  void* dout = host ? st.out(sizeof(double) * K * dim) : out;
+  if (st.rc) return st.rc;
+  hipError_t e = ikg::launch_table_write(dtab, tab.data(), tab.size(), s);
+  if (e == hipSuccess)
+    e = ikg::launch_bezier_eval(dtab, n_points, dim, t_min, t_max, mult, (const double*)dt, K, (double*)dout, s);
+  if (e != hipSuccess) return hip_fail(e, "ikg bezier kernel launch");
+  if (host) st.back(out, dout, sizeof(double) * K * dim);
+  if (st.rc) return st.rc;
+  e = hipStreamSynchronize(s);  // the table is freed on return
+  if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+  return IKG_OK;
+}
+
+void ikg_rollout_params_default(ikg_rollout_params* p) {
+  if (!p) return;
+  ikg_control_params_default(&p->control);
+  p->dt_sim = 1e-3;   // config.py:21
+  p->dt_traj = 1e-2;  // control.py:449, :463: DT = 0.01 per 1 ms simulator tick
+  p->ticks = 0;
+  p->record_every = 0;
+}
+
+int ikg_control_rollout(const ikg_model* model, int device, const void* q0, const void* v0, const void* t0, int64_t B,
+                        const ikg_bezier* q_curve, const ikg_bezier* v_curve, const ikg_rollout_params* params,
+                        const ikg_rollout_out* out, void* stream, uint32_t flags) {
+  g_err[0] = 0;
+  if (!model) return fail(IKG_EINVAL, "model is NULL");
+  if (!out) return fail(IKG_EINVAL, "out is NULL");
+  if (!params) return fail(IKG_EINVAL, "params is NULL");
+  if (B < 0) return fail(IKG_EINVAL, "B must be >= 0");
+  if (B > 0 && !q0) return fail(IKG_EINVAL, "q0 is required");
+  if (B > (int64_t)1 << 40) return fail(IKG_EINVAL, "B too large");
+  if (!model->has_inertia) return fail(IKG_EINVAL, "no body inertias attached (ikg_model_set_inertia)");
+  const int nq = model->desc.nq;
+  int rc = check_bezier(q_curve, nq, "q_curve");
+  if (!rc) rc = check_bezier(v_curve, nq, "v_curve");
+  if (rc) return rc;
+  {
+    const ikg_control_params& c = params->control;
+    const double g[8] = {c.Kp, c.Kv, c.Kf, c.Kt, c.lambda_reg, c.qp_reg, params->dt_sim, params->dt_traj};
+    rc = check_finite<double>(g, 8, "gains / dt");
+    if (!rc) rc = check_finite<double>(c.fc_bias, 12, "fc_bias");
+    if (rc) return rc;
+    if (!(c.lambda_reg > 0) || !(c.qp_reg > 0))
+      return fail(IKG_EINVAL, "lambda_reg and qp_reg must be > 0 (they make the factored matrices positive definite)");
+    if (params->ticks < 0 || params->record_every < 0)
+      return fail(IKG_EINVAL, "ticks and record_every must be >= 0");
+    if ((out->q_hist || out->v_hist || out->tau_hist) && params->record_every == 0)
+      return fail(IKG_EINVAL, "a history output needs record_every > 0");
+  }
+  if (flags & IKG_FLAG_HOST_POINTERS) {  // the device code is built with -ffinite-math-only
+    const int64_t n = B * nq;
+    rc = check_finite<double>(q0, n, "q0");
+    if (!rc && v0) rc = check_finite<double>(v0, n, "v0");
+    if (!rc && t0) rc = check_finite<double>(t0, B, "t0");
+    if (rc) return rc;
+  }
+  DeviceGuard g(device);
+  if (g.rc) return g.rc;
+  if (B == 0) return IKG_OK;
+  return control_rollout(const_cast<ikg_model*>(model), device, q0, v0, t0, B, *q_curve, *v_curve, *params, *out,
+                         (hipStream_t)stream, flags);
+}
+
+}  // extern "C"
+
 // ------------------------------------------------------------ model-specialised kernels
 namespace {
 

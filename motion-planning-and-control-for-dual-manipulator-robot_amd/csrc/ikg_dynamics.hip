@@ -21,7 +21,13 @@
 //   * M_ij = S_j . (Ic_i S_i) for j = i or an ancestor of i, written with its
 //     mirror entry into the workgroup's dense LDS tile (zeroed first), which
 //     is streamed out with 16-byte stores (ikg_control.hip tile_store).
+//
+// Further down: the controller solve (control.py:348-406), forward dynamics
+// qdd = M^-1 (tau - nle), the Bezier desired state (control.py:30-46) and the
+// per-tick step kernel of the closed-loop rollout (control.py:461-463).
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "ikg_dynamics.hpp"
 #include "ikg_launch.hpp"
@@ -291,6 +297,349 @@ hipError_t launch_control_solve(const CtlIn& in, int nq, int64_t B, const KCtl<d
     hipLaunchKernelGGL((ikg_control_solve_kernel<16>), dim3((unsigned)nblocks), dim3(64), lds, s, in, nq, B, prm, o);
   else
     hipLaunchKernelGGL((ikg_control_solve_kernel<32>), dim3((unsigned)nblocks), dim3(64), lds, s, in, nq, B, prm, o);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- forward dynamics
+// qdd = M^-1 (tau - nle): the solve kernel's layout (G lanes per state, M in
+// LDS, one wave per workgroup), lane b = body b = row b.  nle comes from the
+// dynamics kernel (scratch).  M is formed here, each row about its own joint's
+// origin (ikg_dynamics.hpp "M about each joint's own origin": the division by M
+// needs its small rows to their own relative accuracy), straight into LDS:
+// the dynamics kernel's forward pass at zero velocity, then lane b sums the
+// bodies of its subtree as seen from o_b and writes row b with its mirror
+// entries.  Then the factorisation of M and the two substitutions.
+template <int G>
+__global__ __launch_bounds__(64) void ikg_forward_dynamics_kernel(const KModel<double>* __restrict__ m,
+                                                                  const KInertia<double>* __restrict__ in,
+                                                                  const double* __restrict__ q,
+                                                                  const double* __restrict__ nle,
+                                                                  const double* __restrict__ tau, int64_t B,
+                                                                  double* __restrict__ qdd) {
+  using T = double;
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int nq = m->nq;
+  const int lane = threadIdx.x;
+  const int grp = lane / G, b = lane % G, gbase = grp * G;
+  const int64_t p0 = (int64_t)blockIdx.x * (64 / G);
+  const bool live = p0 + grp < B;
+  const int64_t p = live ? p0 + grp : B - 1;
+  const bool body = b < nq;
+  CtlWs<T> f;
+  fd_ws_bind(reinterpret_cast<T*>(smem) + (size_t)grp * fd_ws_len(nq), nq, f);
+  for (int i = b; i < nq * f.ld; i += G) f.M[i] = T(0);
+  if (body) f.rhs[b] = tau[p * nq + b] - nle[p * nq + b];
+  if (b == 0) *f.fail = T(0);
+  // this lane's joint (idle lanes: a joint under the universe that owns no row)
+  const int bi = body ? b : 0;
+  T jR[9], jt[3];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) jR[i] = m->jR[bi][i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) jt[i] = m->jt[bi][i];
+  const int axis = m->jaxis[bi];
+  const int parent = body ? m->jparent[bi] : -1;
+  const uint32_t anc = body ? in->anc[bi] : 0u;
+  const T grav[3] = {in->grav[0], in->grav[1], in->grav[2]};
+  const T ref[3] = {in->ref[0], in->ref[1], in->ref[2]};
+  const int levels = in->levels;
+  T s, c;
+  cw_sincos(body ? q[p * nq + b] : T(0), &s, &c);
+  DynBody<T> uni, me;
+  dyn_universe(grav, ref, uni);
+  me = uni;
+  T S[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
+  const int src = parent >= 0 ? gbase + parent : lane;
+#pragma unroll 1
+  for (int l = 0; l < levels; ++l) {
+    DynBody<T> par;
+    lane_get_n(me.R, src, par.R);
+    lane_get_n(me.o, src, par.o);
+    lane_get_n(me.v, src, par.v);
+    lane_get_n(me.a, src, par.a);
+    if (parent < 0) par = uni;
+    dyn_forward(par, jR, jt, axis, s, c, T(0), me, S);
+  }
+  // the subtree of b as seen from o_b (j ascending, as inertia_matrix_local_state)
+  DynInertia<T> Ic;
+  dyn_inertia_zero(Ic);
+#pragma unroll 1
+  for (int j = 0; j < nq; ++j) {
+    T Rj[9], oj[3];
+    lane_get_n(me.R, gbase + j, Rj);
+    lane_get_n(me.o, gbase + j, oj);
+    const T hj[3] = {in->h[j][0], in->h[j][1], in->h[j][2]};
+    const T Ioj[6] = {in->Io[j][0], in->Io[j][1], in->Io[j][2], in->Io[j][3], in->Io[j][4], in->Io[j][5]};
+    if (body && ((in->anc[j] >> b) & 1)) dyn_inertia_add_about(in->mass[j], hj, Ioj, Rj, oj, me.o, Ic);
+  }
+  T Sb[6], F[6];
+  dyn_subspace_about(me.o, me.o, S + 3, Sb);
+  dyn_apply(Ic, Sb, F);
+  __syncthreads();  // M is zeroed
+#pragma unroll 1
+  for (int j = 0; j < nq; ++j) {
+    T oj[3], aj[3];
+    lane_get_n(me.o, gbase + j, oj);
+    const T a3[3] = {S[3], S[4], S[5]};
+    lane_get_n(a3, gbase + j, aj);
+    if (body && ((anc >> j) & 1)) {
+      T Sj[6];
+      dyn_subspace_about(oj, me.o, aj, Sj);
+      const T x = ddot6(Sj, F);
+      f.M[b * f.ld + j] = x;
+      f.M[j * f.ld + b] = x;
+    }
+  }
+  __syncthreads();
+#pragma unroll 1
+  for (int k = 0; k < nq; ++k) {
+    ldl_step(f.M, f.ld, nq, k, b);
+    __syncthreads();
+  }
+#pragma unroll 1
+  for (int k = 0; k < nq; ++k) {
+    ctl_solve_fwd(f, k, b);
+    __syncthreads();
+  }
+#pragma unroll 1
+  for (int k = nq - 1; k >= 0; --k) {
+    ctl_solve_bwd(f, k, b);
+    __syncthreads();
+  }
+  if (live && body) qdd[p * nq + b] = f.qdd[b];
+}
+
+hipError_t launch_forward_dynamics(const KModel<double>* dm, const KInertia<double>* di, int nq, const void* q,
+                                   const void* nle, const void* tau, int64_t B, void* qdd, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  const int G = nq <= 16 ? 16 : 32;
+  const int64_t nblocks = (B + 64 / G - 1) / (64 / G);
+  if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
+  const size_t lds = sizeof(double) * (64 / G) * fd_ws_len(nq);
+  if (G == 16)
+    hipLaunchKernelGGL((ikg_forward_dynamics_kernel<16>), dim3((unsigned)nblocks), dim3(64), lds, s, dm, di,
+                       (const double*)q, (const double*)nle, (const double*)tau, B, (double*)qdd);
+  else
+    hipLaunchKernelGGL((ikg_forward_dynamics_kernel<32>), dim3((unsigned)nblocks), dim3(64), lds, s, dm, di,
+                       (const double*)q, (const double*)nle, (const double*)tau, B, (double*)qdd);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- Bezier curves
+namespace {
+
+constexpr int kTableChunk = 384;  // doubles per launch: 3 KB of the 4 KB of kernel arguments
+struct TableChunk {
+  double x[kTableChunk];
+};
+
+__device__ inline KBezier<double> curve_q(const RolloutCurves& cv, const double* tab, int nq) {
+  return KBezier<double>{tab, tab + cv.nq_pts * nq, cv.nq_pts, nq, cv.q_tmin, cv.q_tmax, cv.q_mult};
+}
+__device__ inline KBezier<double> curve_v(const RolloutCurves& cv, const double* tab, int nq) {
+  const double* tv = tab + (size_t)cv.nq_pts * (nq + 1);
+  return KBezier<double>{tv, tv + cv.nv_pts * nq, cv.nv_pts, nq, cv.v_tmin, cv.v_tmax, cv.v_mult};
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(128) void ikg_table_write_kernel(double* __restrict__ dst, int n, TableChunk c) {
+  const int i = blockIdx.x * 128 + threadIdx.x;
+  if (i < n) dst[i] = c.x[i];
+}
+
+hipError_t launch_table_write(double* dst, const double* host, size_t n, hipStream_t s) {
+  for (size_t off = 0; off < n; off += kTableChunk) {
+    TableChunk c;
+    const int m = (int)std::min<size_t>(kTableChunk, n - off);
+    std::memcpy(c.x, host + off, sizeof(double) * m);
+    hipLaunchKernelGGL(ikg_table_write_kernel, dim3((m + 127) / 128), dim3(128), 0, s, dst + off, m, c);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// out[k, c] = curve(times[k])[c]: one lane per entry
+__global__ __launch_bounds__(256) void ikg_bezier_eval_kernel(KBezier<double> c, const double* __restrict__ times,
+                                                              int64_t K, double* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= K * c.dim) return;
+  const int64_t k = i / c.dim;
+  out[i] = bezier_eval(c, times[k], (int)(i % c.dim));
+}
+
+hipError_t launch_bezier_eval(const double* table, int n_points, int dim, double t_min, double t_max, double mult,
+                              const double* times, int64_t K, double* out, hipStream_t s) {
+  const KBezier<double> c{table, table + (size_t)n_points * dim, n_points, dim, t_min, t_max, mult};
+  const int64_t rows = ((int64_t)1 << 30) / dim;  // per launch: at most 2^30 entries
+  for (int64_t off = 0; off < K; off += rows) {
+    const int64_t n = std::min(rows, K - off);
+    hipLaunchKernelGGL(ikg_bezier_eval_kernel, dim3((unsigned)((n * dim + 255) / 256)), dim3(256), 0, s, c,
+                       times + off, n, out + off * dim);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// ---------------------------------------------------------------- closed-loop rollout
+// state rows <- the start, and the desired state of tick 0: one lane per (state, joint)
+__global__ __launch_bounds__(256) void ikg_rollout_init_kernel(const double* __restrict__ q0,
+                                                               const double* __restrict__ v0,
+                                                               const double* __restrict__ t0, int nq, int64_t n,
+                                                               StepArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n * nq) return;
+  const int64_t p = i / nq;
+  const int r = (int)(i % nq);
+  const double t = t0 ? t0[p] : a.cv.q_tmin;
+  ((double*)a.q)[i] = q0[i];
+  ((double*)a.v)[i] = v0 ? v0[i] : 0.0;
+  const KBezier<double> cq = curve_q(a.cv, a.cv.table, nq), cv = curve_v(a.cv, a.cv.table, nq);
+  ((double*)a.qdes)[i] = bezier_eval(cq, bezier_clamp(cq, t), r);
+  ((double*)a.vdes)[i] = bezier_eval(cv, bezier_clamp(cv, t), r);
+  if (r == 0) ((double*)a.t)[p] = t;
+}
+
+hipError_t launch_rollout_init(const void* q0, const void* v0, const void* t0, int nq, int64_t n, const StepArgs& a,
+                               hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  const int64_t nblocks = (n * nq + 255) / 256;
+  if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ikg_rollout_init_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, (const double*)q0,
+                     (const double*)v0, (const double*)t0, nq, n, a);
+  return hipGetLastError();
+}
+
+// One tick after the frame-kinematics and dynamics kernels filled the scratch:
+// the solve kernel's layout and phases (lane r = row r = joint r), then on the
+// factor of M the solve left in LDS the forward dynamics qdd = M^-1 (tau - nle),
+// the integrator, the trajectory clock, the desired state of the next tick
+// (Horner over the curves' control points, staged in LDS behind the states'
+// workspaces) and this tick's record.  Groups past the end of the batch work on
+// the last state and store nothing.
+template <int G>
+__global__ __launch_bounds__(64) void ikg_control_step_kernel(CtlIn in, int nq, int64_t B, KCtl<double> prm,
+                                                              StepArgs a) {
+  using T = double;
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int lane = threadIdx.x;
+  const int grp = lane / G, r = lane % G;
+  const int64_t p0 = (int64_t)blockIdx.x * (64 / G);
+  const bool live = p0 + grp < B;
+  const int64_t p = live ? p0 + grp : B - 1;
+  T* base = reinterpret_cast<T*>(smem);
+  CtlWs<T> w, f;
+  ctl_ws_bind(base + (size_t)grp * step_ws_len(nq), nq, w);
+  T* flag = base + (size_t)grp * step_ws_len(nq) + ctl_ws_len(nq);
+  T* tab = base + (size_t)(64 / G) * step_ws_len(nq);
+  const int ntab = (nq + 1) * (a.cv.nq_pts + a.cv.nv_pts);
+  for (int i = lane; i < ntab; i += 64) tab[i] = a.cv.table[i];
+  const T* gM = (const T*)in.M + p * nq * nq;
+  const T* gJ = (const T*)in.J + p * 12 * nq;
+  for (int i = r; i < nq * nq; i += G) w.M[(i / nq) * w.ld + i % nq] = gM[i];
+  for (int i = r; i < 12 * nq; i += G) w.J[(i / nq) * w.ld + i % nq] = gJ[i];
+  if (r < nq) {
+    w.Md[r] = gM[r * nq + r];
+    w.nle[r] = ((const T*)in.nle)[p * nq + r];
+  }
+  if (r < 12) {
+    w.dJv[r] = ((const T*)in.dJv)[p * 12 + r];
+    w.e[r] = ((const T*)in.err)[p * 12 + r];
+    w.ed[r] = ((const T*)in.derr)[p * 12 + r];
+  }
+  const bool row = live && r < nq;
+  T q = row ? ((const T*)a.q)[p * nq + r] : T(0);
+  T v = row ? ((const T*)a.v)[p * nq + r] : T(0);
+  const T t = ((const T*)a.t)[p] + a.dt_traj;
+  __syncthreads();
+#pragma unroll 1
+  for (int k = 0; k < nq; ++k) {
+    ldl_step(w.M, w.ld, nq, k, r);
+    __syncthreads();
+  }
+  ctl_pivots(w, r);
+  __syncthreads();
+  ctl_forward(w, prm, r);
+  __syncthreads();
+  ctl_opspace(w, prm, r);
+  __syncthreads();
+#pragma unroll 1
+  for (int k = 0; k < 6; ++k) {
+    ctl_opspace_step(w, k, r);
+    __syncthreads();
+  }
+  T lam[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
+  ctl_lambda(w, prm, r, lam);
+  __syncthreads();
+  ctl_normal(w, prm, r);
+  __syncthreads();
+#pragma unroll 1
+  for (int k = 0; k < nq; ++k) {
+    ldl_step(w.H, w.ld, nq, k, r);
+    __syncthreads();
+  }
+  ctl_check(w, r);
+  __syncthreads();
+#pragma unroll 1
+  for (int k = 0; k < nq; ++k) {
+    ctl_solve_fwd(w, k, r);
+    __syncthreads();
+  }
+#pragma unroll 1
+  for (int k = nq - 1; k >= 0; --k) {
+    ctl_solve_bwd(w, k, r);
+    __syncthreads();
+  }
+  const T tau = step_rhs(w, prm, flag, r);
+  __syncthreads();
+  fd_view(w, flag, f);
+#pragma unroll 1
+  for (int k = 0; k < nq; ++k) {
+    ctl_solve_fwd(f, k, r);
+    __syncthreads();
+  }
+#pragma unroll 1
+  for (int k = nq - 1; k >= 0; --k) {
+    ctl_solve_bwd(f, k, r);
+    __syncthreads();
+  }
+  if (!live) return;
+  if (r < nq) {
+    step_integrate(a.dt_sim, f.qdd[r], q, v);
+    ((T*)a.q)[p * nq + r] = q;
+    ((T*)a.v)[p * nq + r] = v;
+    const KBezier<T> cq = curve_q(a.cv, tab, nq), cv = curve_v(a.cv, tab, nq);
+    ((T*)a.qdes)[p * nq + r] = bezier_eval(cq, bezier_clamp(cq, t), r);
+    ((T*)a.vdes)[p * nq + r] = bezier_eval(cv, bezier_clamp(cv, t), r);
+    if (a.slot >= 0) {
+      const int64_t h = (p * a.R + a.slot) * nq + r;
+      if (a.q_hist) ((T*)a.q_hist)[h] = q;
+      if (a.v_hist) ((T*)a.v_hist)[h] = v;
+      if (a.tau_hist) ((T*)a.tau_hist)[h] = tau;
+    }
+  }
+  if (r == 0) ((T*)a.t)[p] = t;
+}
+
+hipError_t launch_control_step(const CtlIn& in, int nq, int64_t B, const KCtl<double>& prm, const StepArgs& a,
+                               hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  const int G = nq <= 16 ? 16 : 32;
+  const int64_t nblocks = (B + 64 / G - 1) / (64 / G);
+  if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
+  const size_t lds =
+      sizeof(double) * ((64 / G) * step_ws_len(nq) + rollout_table_len(nq, a.cv.nq_pts, a.cv.nv_pts));
+  if (lds > 65536) {  // long curves on a wide model: above the default limit of dynamic LDS
+    const void* fn = G == 16 ? (const void*)ikg_control_step_kernel<16> : (const void*)ikg_control_step_kernel<32>;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  if (G == 16)
+    hipLaunchKernelGGL((ikg_control_step_kernel<16>), dim3((unsigned)nblocks), dim3(64), lds, s, in, nq, B, prm, a);
+  else
+    hipLaunchKernelGGL((ikg_control_step_kernel<32>), dim3((unsigned)nblocks), dim3(64), lds, s, in, nq, B, prm, a);
   return hipGetLastError();
 }
 

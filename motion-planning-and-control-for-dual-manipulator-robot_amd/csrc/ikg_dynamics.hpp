@@ -350,6 +350,69 @@ inline void dynamics_state(const KModel<T>& m, const KInertia<T>& in, const T* q
   }
 }
 
+// ---------------------------------------------------------------- M about each joint's own origin
+// Forward dynamics divides by M, so it needs the SMALL entries of M (the wrist
+// rows, 1e-4 of max|M|) to their own relative accuracy.  About one common
+// reference point every body's inertia carries m |o|^2 terms that cancel in
+// those entries: M above is within 4e-16 of max|M|, an absolute error the wrist
+// rows see in full, and cond(M) ~ 1e4 carries it into qdd (measured 1.8e-13 of
+// max|qdd| against 2e-15 for a body-local M).  So row i is formed about joint
+// i's own origin o_i, where only distances inside the subtree of i appear:
+//   Ic_i = sum_{j in subtree(i)} inertia of body j about o_i   (dyn_inertia_world with o = o_j - o_i)
+//   F_i  = Ic_i [0; a_i],   M_ij = [(o_j - o_i) x a_j; a_j] . F_i   for j = i or an ancestor of i.
+// motion subspace of joint j (origin oj, world axis aj) about the point oi
+template <typename T>
+IKG_HD inline void dyn_subspace_about(const T* oj, const T* oi, const T* aj, T* S) {
+  const T d[3] = {oj[0] - oi[0], oj[1] - oi[1], oj[2] - oi[2]};
+  dcross(d, aj, S);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) S[3 + i] = aj[i];
+}
+
+// body j (placement Rj, oj) as seen from the point oi, added to Ic
+template <typename T>
+IKG_HD inline void dyn_inertia_add_about(T m, const T* h, const T* Io, const T* Rj, const T* oj, const T* oi,
+                                         DynInertia<T>& Ic) {
+  const T d[3] = {oj[0] - oi[0], oj[1] - oi[1], oj[2] - oi[2]};
+  DynInertia<T> W;
+  dyn_inertia_world(m, h, Io, Rj, d, W);
+  dyn_inertia_add(Ic, W);
+}
+
+// One state on the host, in the forward-dynamics kernel's order: M [nq,nq], both triangles
+template <typename T>
+inline void inertia_matrix_local_state(const KModel<T>& m, const KInertia<T>& in, const T* q, T* M) {
+  const int nq = m.nq;
+  DynBody<T> body[kMaxNq];
+  T S[kMaxNq][6];
+  DynBody<T> uni;
+  dyn_universe(in.grav, in.ref, uni);
+  for (int i = 0; i < nq; ++i) {
+    T s, c;
+    cw_sincos(q[i], &s, &c);
+    const DynBody<T>& par = m.jparent[i] >= 0 ? body[m.jparent[i]] : uni;
+    dyn_forward(par, m.jR[i], m.jt[i], m.jaxis[i], s, c, T(0), body[i], S[i]);
+  }
+  for (int i = 0; i < nq * nq; ++i) M[i] = T(0);
+  for (int i = 0; i < nq; ++i) {
+    DynInertia<T> Ic;
+    dyn_inertia_zero(Ic);
+    for (int j = 0; j < nq; ++j)
+      if ((in.anc[j] >> i) & 1) dyn_inertia_add_about(in.mass[j], in.h[j], in.Io[j], body[j].R, body[j].o, body[i].o, Ic);
+    T Si[6], F[6];
+    dyn_subspace_about(body[i].o, body[i].o, S[i] + 3, Si);
+    dyn_apply(Ic, Si, F);
+    for (int j = 0; j < nq; ++j)
+      if ((in.anc[i] >> j) & 1) {
+        T Sj[6];
+        dyn_subspace_about(body[j].o, body[i].o, S[j] + 3, Sj);
+        const T x = ddot6(Sj, F);
+        M[i * nq + j] = x;
+        M[j * nq + i] = x;
+      }
+  }
+}
+
 // ---------------------------------------------------------------- controller solve (control.py:348-406)
 // Per state, from M, nle (above) and the kinematic terms J [12,nq], dJ v, e,
 // e' of ikg_frame_kinematics_batch (LOCAL_WORLD_ALIGNED):
@@ -561,26 +624,12 @@ IKG_HD inline T ctl_tau(const CtlWs<T>& w, const KCtl<T>& p, int r) {
   return ((p.zero_tau_mask >> r) & 1u) ? T(0) : acc;
 }
 
-// One state on the host: the phases in the kernel's order.  M [nq,nq], nle
-// [nq], J [12,nq], dJv / e / ed [12] in; outputs may be null.
+// the solve's phases for one state on the host, in the kernel's order (the
+// workspace is loaded); Lambda [2,36] may be null
 template <typename T>
-inline void control_state(int nq, const KCtl<T>& p, const T* M, const T* nle, const T* J, const T* dJv, const T* e,
-                          const T* ed, T* tau, T* qdd, T* xdd, T* Lambda, T* fc) {
-  T buf[2 * kMaxNq * (kMaxNq + 1) + 24 * (kMaxNq + 1) + 6 * kMaxNq + 146];
-  CtlWs<T> w;
-  ctl_ws_bind(buf, nq, w);
+inline void control_solve_phases(const CtlWs<T>& w, const KCtl<T>& p, T* Lambda) {
+  const int nq = w.nq;
   const int R = nq > 12 ? nq : 12;
-  for (int r = 0; r < nq; ++r) {
-    for (int c = 0; c < nq; ++c) w.M[r * w.ld + c] = M[r * nq + c];
-    w.Md[r] = M[r * nq + r];
-    w.nle[r] = nle[r];
-  }
-  for (int k = 0; k < 12; ++k) {
-    for (int r = 0; r < nq; ++r) w.J[k * w.ld + r] = J[k * nq + r];
-    w.dJv[k] = dJv[k];
-    w.e[k] = e[k];
-    w.ed[k] = ed[k];
-  }
   for (int k = 0; k < nq; ++k)
     for (int r = 0; r < R; ++r) ldl_step(w.M, w.ld, nq, k, r);
   for (int r = 0; r < R; ++r) ctl_pivots(w, r);
@@ -602,6 +651,35 @@ inline void control_state(int nq, const KCtl<T>& p, const T* M, const T* nle, co
     for (int r = 0; r < R; ++r) ctl_solve_fwd(w, k, r);
   for (int k = nq - 1; k >= 0; --k)
     for (int r = 0; r < R; ++r) ctl_solve_bwd(w, k, r);
+}
+
+template <typename T>
+inline void control_ws_load(const CtlWs<T>& w, const T* M, const T* nle, const T* J, const T* dJv, const T* e,
+                            const T* ed) {
+  const int nq = w.nq;
+  for (int r = 0; r < nq; ++r) {
+    for (int c = 0; c < nq; ++c) w.M[r * w.ld + c] = M[r * nq + c];
+    w.Md[r] = M[r * nq + r];
+    w.nle[r] = nle[r];
+  }
+  for (int k = 0; k < 12; ++k) {
+    for (int r = 0; r < nq; ++r) w.J[k * w.ld + r] = J[k * nq + r];
+    w.dJv[k] = dJv[k];
+    w.e[k] = e[k];
+    w.ed[k] = ed[k];
+  }
+}
+
+// One state on the host: the phases in the kernel's order.  M [nq,nq], nle
+// [nq], J [12,nq], dJv / e / ed [12] in; outputs may be null.
+template <typename T>
+inline void control_state(int nq, const KCtl<T>& p, const T* M, const T* nle, const T* J, const T* dJv, const T* e,
+                          const T* ed, T* tau, T* qdd, T* xdd, T* Lambda, T* fc) {
+  T buf[2 * kMaxNq * (kMaxNq + 1) + 24 * (kMaxNq + 1) + 6 * kMaxNq + 146];
+  CtlWs<T> w;
+  ctl_ws_bind(buf, nq, w);
+  control_ws_load(w, M, nle, J, dJv, e, ed);
+  control_solve_phases(w, p, Lambda);
   for (int r = 0; r < nq; ++r) {
     const T t = ctl_tau(w, p, r);
     if (tau) tau[r] = t;
@@ -611,6 +689,152 @@ inline void control_state(int nq, const KCtl<T>& p, const T* M, const T* nle, co
     if (xdd) xdd[k] = w.xdd[k];
     if (fc) fc[k] = w.fc[k];
   }
+}
+
+// ---------------------------------------------------------------- Bezier desired state (control.py:30-46)
+// The reference's Bezier.__call__ / eval_horner, operation for operation:
+//   u = (t - T_min) / (T_max - T_min);  u_op = 1 - u;  tmp = P_0 u_op
+//   for i in 1 .. degree - 1:  tn *= u;  bc *= (degree - i + 1) / i;  tmp = (tmp + (tn bc) P_i) u_op
+//   result = (tmp + (tn u) P_degree) mult
+// and mult P_0 for a curve of two control points (the reference's size_ == 1
+// branch).  The binomial factors bc_i do not depend on t: bezier_coeffs builds
+// them once on the host with the reference's operations.  P is [n, dim]
+// row-major, one column per joint; the caller keeps t in [t_min, t_max].
+constexpr int kMaxBezier = 64;  // control points of a curve
+
+template <typename T>
+struct KBezier {
+  const T* P;   // [n, dim]
+  const T* bc;  // [n]; bc[0] = 1
+  int n, dim;
+  T t_min, t_max, mult;
+};
+
+inline void bezier_coeffs(int n, double* bc) {
+  const int degree = n - 1;
+  double b = 1.0;
+  bc[0] = 1.0;
+  for (int i = 1; i < n; ++i) {
+    b *= (double)(degree - i + 1) / (double)i;
+    bc[i] = b;
+  }
+}
+
+template <typename T>
+IKG_HD inline T bezier_clamp(const KBezier<T>& c, T t) {
+  return t < c.t_min ? c.t_min : (t > c.t_max ? c.t_max : t);
+}
+
+// No contraction into fused multiply-adds: the init kernel, the step kernel,
+// the evaluation kernel and the host all round every product as the reference's
+// numpy does, so a desired state does not depend on which of them computed it
+// (a rollout of 8 ticks equals 8 rollouts of 1 tick to the bit).
+template <typename T>
+IKG_HD inline T bezier_eval(const KBezier<T>& c, T t, int col) {
+#pragma clang fp contract(off)
+  if (c.n == 2) return c.mult * c.P[col];
+  const T u = (t - c.t_min) / (c.t_max - c.t_min);
+  const T uo = T(1) - u;
+  T tn = T(1);
+  T tmp = c.P[col] * uo;
+  for (int i = 1; i < c.n - 1; ++i) {
+    tn *= u;
+    tmp = (tmp + (tn * c.bc[i]) * c.P[i * c.dim + col]) * uo;
+  }
+  return (tmp + (tn * u) * c.P[(c.n - 1) * c.dim + col]) * c.mult;
+}
+
+// ---------------------------------------------------------------- forward dynamics and one closed-loop tick
+// qdd = M^-1 (tau - nle) with the L D L^T factor of M (ldl_step) and the
+// substitution phases of the QP (ctl_solve_fwd / ctl_solve_bwd): fd_view
+// presents the factor as their H, with a pivot flag of its own (the QP's flag
+// zeroes the QP's answer, not the plant's).
+template <typename T>
+IKG_HD inline void fd_view(const CtlWs<T>& w, T* flag, CtlWs<T>& f) {
+  f = w;
+  f.H = w.M;
+  f.fail = flag;
+}
+
+// a state's workspace of the closed-loop step: the solve's plus the flag above
+IKG_HD inline int step_ws_len(int nq) { return ctl_ws_len(nq) + 2; }
+
+// row r: the applied torque and the right-hand side tau - nle of the forward dynamics
+template <typename T>
+IKG_HD inline T step_rhs(const CtlWs<T>& w, const KCtl<T>& p, T* flag, int r) {
+  T t = T(0);
+  if (r < w.nq) {
+    t = ctl_tau(w, p, r);
+    w.rhs[r] = t - w.nle[r];
+  }
+  if (r == 0) *flag = T(0);
+  return t;
+}
+
+// semi-implicit Euler (Bullet's scheme): v += dt qdd, then q += dt v
+template <typename T>
+IKG_HD inline void step_integrate(T dt, T qdd, T& q, T& v) {
+  v += dt * qdd;
+  q += dt * v;
+}
+
+// the forward-dynamics workspace on its own: M [nq*ld] (factored in place), rhs, qdd [nq], flag
+IKG_HD inline int fd_ws_len(int nq) { return nq * (nq | 1) + 2 * nq + 2; }
+
+template <typename T>
+IKG_HD inline void fd_ws_bind(T* base, int nq, CtlWs<T>& f) {
+  const int ld = nq | 1;
+  f.nq = nq;
+  f.ld = ld;
+  f.M = f.H = base;
+  f.rhs = base + nq * ld;
+  f.qdd = f.rhs + nq;
+  f.fail = f.qdd + nq;
+  f.Md = f.Mr = f.Ms = f.J = f.Z = f.A = f.nle = f.e = f.ed = f.dJv = f.fc = f.xdd = nullptr;
+}
+
+template <typename T>
+inline void fd_substitute(const CtlWs<T>& f) {
+  const int nq = f.nq;
+  for (int k = 0; k < nq; ++k)
+    for (int r = 0; r < nq; ++r) ctl_solve_fwd(f, k, r);
+  for (int k = nq - 1; k >= 0; --k)
+    for (int r = 0; r < nq; ++r) ctl_solve_bwd(f, k, r);
+}
+
+// One state on the host: qdd = M^-1 (tau - nle), the forward-dynamics kernel's order
+template <typename T>
+inline void forward_dynamics_state(int nq, const T* M, const T* nle, const T* tau, T* qdd) {
+  T buf[kMaxNq * (kMaxNq + 1) + 2 * kMaxNq + 2];
+  CtlWs<T> f;
+  fd_ws_bind(buf, nq, f);
+  for (int r = 0; r < nq; ++r) {
+    for (int c = 0; c < nq; ++c) f.M[r * f.ld + c] = M[r * nq + c];
+    f.rhs[r] = tau[r] - nle[r];
+  }
+  *f.fail = T(0);
+  for (int k = 0; k < nq; ++k)
+    for (int r = 0; r < nq; ++r) ldl_step(f.M, f.ld, nq, k, r);
+  fd_substitute(f);
+  for (int r = 0; r < nq; ++r) qdd[r] = f.qdd[r];
+}
+
+// One closed-loop tick of one state on the host, the step kernel's order: the
+// solve's phases, tau, the forward dynamics on the factor of M the solve left,
+// the integrator.  q, v [nq] are advanced in place; tau [nq] out.
+template <typename T>
+inline void control_step_state(int nq, const KCtl<T>& p, const T* M, const T* nle, const T* J, const T* dJv,
+                               const T* e, const T* ed, T dt, T* q, T* v, T* tau) {
+  T buf[2 * kMaxNq * (kMaxNq + 1) + 24 * (kMaxNq + 1) + 6 * kMaxNq + 148];
+  CtlWs<T> w, f;
+  ctl_ws_bind(buf, nq, w);
+  T* flag = buf + ctl_ws_len(nq);
+  control_ws_load(w, M, nle, J, dJv, e, ed);
+  control_solve_phases(w, p, (T*)nullptr);
+  for (int r = 0; r < nq; ++r) tau[r] = step_rhs(w, p, flag, r);
+  fd_view(w, flag, f);
+  fd_substitute(f);
+  for (int r = 0; r < nq; ++r) step_integrate(dt, f.qdd[r], q[r], v[r]);
 }
 
 }  // namespace ikg

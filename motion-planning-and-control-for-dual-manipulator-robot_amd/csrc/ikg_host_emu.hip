@@ -2,7 +2,9 @@
 // never called by libikgrasp.so): runs the exact stage functions of
 // ikg_device.hpp for both arm lanes of a problem on the CPU, in the order the
 // kernel's lanes execute them, so kernel numerics can be inspected without a
-// GPU.  Built as libikgrasp_emu.so; used by tests/test_host_emu.py.
+// GPU.  Built as libikgrasp_emu.so; used by tests/test_host_emu.py.  Further
+// down: the collision, dynamics, controller and closed-loop rollout arithmetic
+// on the same terms (tests/test_collision.py, test_dynamics.py, test_rollout.py).
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -493,6 +495,220 @@ extern "C" int ikg_emu_control_torque(const ikg_model_desc* d, const ikg_inertia
                                tau ? tau + nq * i : nullptr, qdd ? qdd + nq * i : nullptr,
                                xdd ? xdd + 12 * i : nullptr, Lambda ? Lambda + 72 * i : nullptr,
                                fc ? fc + 12 * i : nullptr);
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------- closed-loop rollout on the CPU
+// The kinematic terms of one state (J [12,nq], dJ v, e, e' [12],
+// LOCAL_WORLD_ALIGNED) in the frame-kinematics kernel's point-velocity form
+//   J_k = [a_k x (p - o_k); a_k],  dJ_k = [a'_k x (p - o_k) + a_k x (p' - o'_k); a'_k],  a'_k = w_parent x a_k
+// walked over the tree tables (jR / jt / jaxis / jparent).  The kernel's chain
+// functions are device-only and specialised per model class, so this is a
+// restatement of them, not the same code: an emulated rollout agrees with the
+// GPU to rounding, not to the bit.  Everything after the kinematic terms runs
+// the shared phase functions of ikg_dynamics.hpp.
+namespace {
+
+template <typename T>
+struct EmuHand {
+  T R[9], p[3], pd[3], w[3];
+};
+
+template <typename T>
+void emu_frame_pass(const ikg::KModel<T>& m, const T* q, const T* v, EmuHand<T> hand[2], T* J, T* dJv) {
+  using namespace ikg;
+  const int nq = m.nq;
+  T R[kMaxNq][9], o[kMaxNq][3], od[kMaxNq][3], w[kMaxNq][3], a[kMaxNq][3], ad[kMaxNq][3];
+  for (int i = 0; i < nq; ++i) {
+    const int p = m.jparent[i];
+    T Rp[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, op[3] = {0, 0, 0}, odp[3] = {0, 0, 0}, wp[3] = {0, 0, 0};
+    if (p >= 0) {
+      std::memcpy(Rp, R[p], sizeof(Rp));
+      std::memcpy(op, o[p], sizeof(op));
+      std::memcpy(odp, od[p], sizeof(odp));
+      std::memcpy(wp, w[p], sizeof(wp));
+    }
+    T d[3], wd[3], s, c;
+    matvec3(Rp, m.jt[i], d);
+    dcross(wp, d, wd);
+    matmul3(Rp, m.jR[i], R[i]);
+    column(R[i], m.jaxis[i], a[i]);
+    cw_sincos(q[i], &s, &c);
+    rotate_axis(R[i], m.jaxis[i], s, c);
+    dcross(wp, a[i], ad[i]);
+    for (int k = 0; k < 3; ++k) {
+      o[i][k] = op[k] + d[k];
+      od[i][k] = odp[k] + wd[k];
+      w[i][k] = wp[k] + a[i][k] * (v ? v[i] : T(0));
+    }
+  }
+  if (J)
+    for (int i = 0; i < 12 * nq; ++i) J[i] = T(0);
+  for (int h = 0; h < 2; ++h) {
+    const int j = m.arm_q[h][kArmDof - 1];
+    EmuHand<T>& f = hand[h];
+    T d[3], wd[3];
+    matvec3(R[j], m.hand_t[h], d);
+    dcross(w[j], d, wd);
+    matmul3(R[j], m.hand_R[h], f.R);
+    for (int k = 0; k < 3; ++k) {
+      f.p[k] = o[j][k] + d[k];
+      f.pd[k] = od[j][k] + wd[k];
+      f.w[k] = w[j][k];
+    }
+    if (!J) continue;
+    int chain[kMaxNq], n = 0;
+    for (int k = j; k >= 0; k = m.jparent[k]) chain[n++] = k;
+    T acc[6] = {0, 0, 0, 0, 0, 0};
+    for (int c = n - 1; c >= 0; --c) {  // root first, as the kernel accumulates dJ v
+      const int k = chain[c];
+      T r[3], rd[3], lin[3], t1[3], t2[3];
+      for (int i = 0; i < 3; ++i) {
+        r[i] = f.p[i] - o[k][i];
+        rd[i] = f.pd[i] - od[k][i];
+      }
+      dcross(a[k], r, lin);
+      dcross(ad[k], r, t1);
+      dcross(a[k], rd, t2);
+      for (int i = 0; i < 3; ++i) {
+        J[(6 * h + i) * nq + k] = lin[i];
+        J[(6 * h + 3 + i) * nq + k] = a[k][i];
+        acc[i] += (t1[i] + t2[i]) * (v ? v[k] : T(0));
+        acc[3 + i] += ad[k][i] * (v ? v[k] : T(0));
+      }
+    }
+    for (int i = 0; i < 6; ++i) dJv[6 * h + i] = acc[i];
+  }
+}
+
+template <typename T>
+void emu_frame_terms(const ikg::KModel<T>& m, const T* q, const T* v, const T* qd, const T* vd, T* J, T* dJv, T* err,
+                     T* derr) {
+  using namespace ikg;
+  EmuHand<T> f[2], fd[2];
+  emu_frame_pass(m, q, v, f, J, dJv);
+  emu_frame_pass(m, qd, vd, fd, (T*)nullptr, (T*)nullptr);
+  for (int h = 0; h < 2; ++h) {
+    T Re[9], zero[3] = {0, 0, 0}, lg[6];
+    matmul3_nt(fd[h].R, f[h].R, Re);
+    log6(Re, zero, lg);
+    for (int i = 0; i < 3; ++i) {
+      err[6 * h + i] = fd[h].p[i] - f[h].p[i];
+      err[6 * h + 3 + i] = lg[3 + i];
+      derr[6 * h + i] = fd[h].pd[i] - f[h].pd[i];
+      derr[6 * h + 3 + i] = fd[h].w[i] - f[h].w[i];
+    }
+  }
+}
+
+bool emu_curve_ok(const ikg_bezier* c) {
+  return c && c->points && c->n_points >= 2 && c->n_points <= ikg::kMaxBezier && c->t_max > c->t_min;
+}
+
+}  // namespace
+
+// ikg_frame_kinematics_batch's J, dJ v, err, derr (LOCAL_WORLD_ALIGNED, fp64) by the restatement above
+extern "C" int ikg_emu_frame_terms(const ikg_model_desc* d, const double* q, const double* v, const double* qd,
+                                   const double* vd, int64_t B, double* J, double* dJv, double* err, double* derr) {
+  static thread_local ikg::KModel<double> m;
+  ikg::build_kmodel<double>(*d, m);
+  const int nq = d->nq;
+  for (int64_t i = 0; i < B; ++i)
+    emu_frame_terms<double>(m, q + nq * i, v ? v + nq * i : nullptr, qd + nq * i, vd ? vd + nq * i : nullptr,
+                            J + 12 * nq * i, dJv + 12 * i, err + 12 * i, derr + 12 * i);
+  return 0;
+}
+
+// ikg_forward_dynamics_batch on the CPU: nle of dynamics_state, M about each
+// joint's own origin (inertia_matrix_local_state), then the forward-dynamics kernel's phases
+extern "C" int ikg_emu_forward_dynamics(const ikg_model_desc* d, const ikg_inertia_desc* id, const double* q,
+                                        const double* v, const double* tau, int64_t B, double* qdd) {
+  const char* why = "";
+  if (ikg::check_inertia_desc(*id, d->nq, &why) >= 0) return -1;
+  static thread_local ikg::KModel<double> m;
+  static thread_local ikg::KInertia<double> in;
+  ikg::build_kmodel<double>(*d, m);
+  ikg::build_kinertia<double>(*d, *id, in);
+  const int nq = d->nq;
+  for (int64_t i = 0; i < B; ++i) {
+    double M[ikg::kMaxNq * ikg::kMaxNq], nle[ikg::kMaxNq];
+    ikg::dynamics_state<double>(m, in, q + nq * i, v ? v + nq * i : nullptr, nullptr, nle, nullptr);
+    ikg::inertia_matrix_local_state<double>(m, in, q + nq * i, M);
+    ikg::forward_dynamics_state<double>(nq, M, nle, tau + nq * i, qdd + nq * i);
+  }
+  return 0;
+}
+
+// ikg_bezier_eval_batch with host pointers on the CPU (bezier_eval); -1 where the entry returns IKG_EINVAL
+extern "C" int ikg_emu_bezier(const double* points, int32_t n_points, int32_t dim, double t_min, double t_max,
+                              double mult, const double* times, int64_t K, double* out) {
+  const ikg_bezier c{points, n_points, t_min, t_max, mult};
+  if (!emu_curve_ok(&c) || dim < 1 || dim > IKG_MAX_NQ) return -1;
+  for (int64_t k = 0; k < K; ++k)
+    if (!(times[k] >= t_min && times[k] <= t_max)) return -1;
+  double bc[ikg::kMaxBezier];
+  ikg::bezier_coeffs(n_points, bc);
+  const ikg::KBezier<double> kb{points, bc, n_points, dim, t_min, t_max, mult};
+  for (int64_t k = 0; k < K; ++k)
+    for (int j = 0; j < dim; ++j) out[k * dim + j] = ikg::bezier_eval(kb, times[k], j);
+  return 0;
+}
+
+// ikg_control_rollout on the CPU: per state and tick the kinematic terms
+// (above), dynamics_state and control_step_state, the clock and the curves.
+extern "C" int ikg_emu_control_rollout(const ikg_model_desc* d, const ikg_inertia_desc* id, const double* q0,
+                                       const double* v0, const double* t0, int64_t B, const ikg_bezier* bq,
+                                       const ikg_bezier* bv, const ikg_rollout_params* p,
+                                       const ikg_rollout_out* out) {
+  const char* why = "";
+  if (ikg::check_inertia_desc(*id, d->nq, &why) >= 0) return -1;
+  if (!emu_curve_ok(bq) || !emu_curve_ok(bv) || p->ticks < 0 || p->record_every < 0) return -1;
+  if ((out->q_hist || out->v_hist || out->tau_hist) && p->record_every == 0) return -1;
+  static thread_local ikg::KModel<double> m;
+  static thread_local ikg::KInertia<double> in;
+  ikg::build_kmodel<double>(*d, m);
+  ikg::build_kinertia<double>(*d, *id, in);
+  const ikg::KCtl<double> prm = ikg::make_kctl<double>(p->control);
+  const int nq = d->nq;
+  double bcq[ikg::kMaxBezier], bcv[ikg::kMaxBezier];
+  ikg::bezier_coeffs(bq->n_points, bcq);
+  ikg::bezier_coeffs(bv->n_points, bcv);
+  const ikg::KBezier<double> cq{bq->points, bcq, bq->n_points, nq, bq->t_min, bq->t_max, bq->mult};
+  const ikg::KBezier<double> cv{bv->points, bcv, bv->n_points, nq, bv->t_min, bv->t_max, bv->mult};
+  const int64_t every = p->record_every, R = every > 0 ? p->ticks / every : 0;
+  for (int64_t i = 0; i < B; ++i) {
+    double q[ikg::kMaxNq], v[ikg::kMaxNq], qd[ikg::kMaxNq], vd[ikg::kMaxNq], tau[ikg::kMaxNq];
+    double t = t0 ? t0[i] : bq->t_min;
+    for (int j = 0; j < nq; ++j) {
+      q[j] = q0[nq * i + j];
+      v[j] = v0 ? v0[nq * i + j] : 0.0;
+    }
+    for (int64_t k = 0; k <= p->ticks; ++k) {
+      for (int j = 0; j < nq; ++j) {
+        qd[j] = ikg::bezier_eval(cq, ikg::bezier_clamp(cq, t), j);
+        vd[j] = ikg::bezier_eval(cv, ikg::bezier_clamp(cv, t), j);
+      }
+      if (k == p->ticks) break;
+      double M[ikg::kMaxNq * ikg::kMaxNq], nle[ikg::kMaxNq], J[12 * ikg::kMaxNq], dJv[12], e[12], ed[12];
+      emu_frame_terms<double>(m, q, v, qd, vd, J, dJv, e, ed);
+      ikg::dynamics_state<double>(m, in, q, v, M, nle, nullptr);
+      ikg::control_step_state<double>(nq, prm, M, nle, J, dJv, e, ed, p->dt_sim, q, v, tau);
+      t += p->dt_traj;
+      if (R && (k + 1) % every == 0) {
+        const int64_t h = (i * R + (k + 1) / every - 1) * nq;
+        for (int j = 0; j < nq; ++j) {
+          if (out->q_hist) ((double*)out->q_hist)[h + j] = q[j];
+          if (out->v_hist) ((double*)out->v_hist)[h + j] = v[j];
+          if (out->tau_hist) ((double*)out->tau_hist)[h + j] = tau[j];
+        }
+      }
+    }
+    for (int j = 0; j < nq; ++j) {
+      if (out->q) ((double*)out->q)[nq * i + j] = q[j];
+      if (out->v) ((double*)out->v)[nq * i + j] = v[j];
+    }
+    if (out->t) ((double*)out->t)[i] = t;
   }
   return 0;
 }

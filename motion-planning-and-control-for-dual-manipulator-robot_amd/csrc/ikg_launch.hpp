@@ -511,4 +511,41 @@ struct CtlOut {
 hipError_t launch_control_solve(const CtlIn& in, int nq, int64_t B, const KCtl<double>& prm, const CtlOut& o,
                                 hipStream_t s);
 
+// closed-loop rollout (ikg_dynamics.hip).  The two curves' control points and
+// binomial factors sit in one device table: [Pq (nq_pts x nq)] [bcq (nq_pts)]
+// [Pv (nv_pts x nq)] [bcv (nv_pts)].
+struct RolloutCurves {
+  const double* table;
+  int nq_pts, nv_pts;
+  double q_tmin, q_tmax, q_mult;
+  double v_tmin, v_tmax, v_mult;
+};
+inline size_t rollout_table_len(int nq, int nq_pts, int nv_pts) { return (size_t)(nq + 1) * (nq_pts + nv_pts); }
+
+// per-tick arguments of the step kernel (device, fp64): the state rows are
+// advanced in place, the desired state is rewritten for the next tick
+struct StepArgs {
+  void *q, *v;        // [n,nq]
+  void* t;            // [n]
+  void *qdes, *vdes;  // [n,nq]
+  RolloutCurves cv;
+  double dt_sim, dt_traj;
+  void *q_hist, *v_hist, *tau_hist;  // [n,R,nq] or null
+  int64_t R, slot;                   // this tick's record (slot < 0: none)
+};
+// dst[0..n) = host[0..n) through kernel arguments: capturable, and the host
+// array is free again when the call returns
+hipError_t launch_table_write(double* dst, const double* host, size_t n, hipStream_t s);
+// table: [P (n_points x dim)] [bc (n_points)]; times [K] inside [t_min, t_max]
+hipError_t launch_bezier_eval(const double* table, int n_points, int dim, double t_min, double t_max, double mult,
+                              const double* times, int64_t K, double* out, hipStream_t s);
+// nle [B,nq] from launch_dynamics; M is formed inside (about each joint's own origin)
+hipError_t launch_forward_dynamics(const KModel<double>* dm, const KInertia<double>* di, int nq, const void* q,
+                                   const void* nle, const void* tau, int64_t B, void* qdd, hipStream_t s);
+// state <- (q0, v0, t0 or the q curve's t_min) and the desired state of tick 0
+hipError_t launch_rollout_init(const void* q0, const void* v0, const void* t0, int nq, int64_t n, const StepArgs& a,
+                               hipStream_t s);
+hipError_t launch_control_step(const CtlIn& in, int nq, int64_t B, const KCtl<double>& prm, const StepArgs& a,
+                               hipStream_t s);
+
 }  // namespace ikg

@@ -110,12 +110,30 @@ class ControlOut(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("tau", "qdd", "xdd", "Lambda", "fc")]
 
 
+class Bezier(C.Structure):
+    """ikg_bezier: a curve's control points (host array [n_points, nq]), range and multiplier."""
+    _fields_ = [("points", C.c_void_p), ("n_points", C.c_int32), ("t_min", C.c_double), ("t_max", C.c_double),
+                ("mult", C.c_double)]
+
+
+class RolloutParams(C.Structure):
+    """ikg_rollout_params: the controller's parameters, the two clocks, the horizon."""
+    _fields_ = [("control", ControlParams), ("dt_sim", C.c_double), ("dt_traj", C.c_double), ("ticks", C.c_int32),
+                ("record_every", C.c_int32)]
+
+
+class RolloutOut(C.Structure):
+    """ikg_rollout_out: optional output pointers of ikg_control_rollout."""
+    _fields_ = [(name, C.c_void_p) for name in ("q", "v", "t", "q_hist", "v_hist", "tau_hist")]
+
+
 EXPORTS = [
     "ikg_model_create", "ikg_model_destroy", "ikg_params_default", "ikg_solve_batch",
     "ikg_solve_multistart", "ikg_fk_batch", "ikg_log6_batch", "ikg_last_error", "ikg_version",
     "ikg_model_set_collision", "ikg_collision_batch", "ikg_distance_batch", "ikg_target_env_batch",
     "ikg_frame_kinematics_batch", "ikg_model_specialize", "ikg_model_is_specialized", "ikg_model_trim",
     "ikg_model_set_inertia", "ikg_dynamics_batch", "ikg_control_params_default", "ikg_control_torque_batch",
+    "ikg_forward_dynamics_batch", "ikg_bezier_eval_batch", "ikg_rollout_params_default", "ikg_control_rollout",
 ]
 
 _lib = None
@@ -188,6 +206,16 @@ def load() -> C.CDLL:
     lib.ikg_control_torque_batch.argtypes = [vp, i32, vp, vp, vp, vp, i64, C.POINTER(ControlParams),
                                              C.POINTER(ControlOut), vp, C.c_uint32]
     lib.ikg_control_torque_batch.restype = i32
+    lib.ikg_forward_dynamics_batch.argtypes = [vp, i32, vp, vp, vp, i64, vp, vp, C.c_uint32]
+    lib.ikg_forward_dynamics_batch.restype = i32
+    lib.ikg_bezier_eval_batch.argtypes = [i32, vp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, vp, i64,
+                                          vp, vp, C.c_uint32]
+    lib.ikg_bezier_eval_batch.restype = i32
+    lib.ikg_rollout_params_default.argtypes = [C.POINTER(RolloutParams)]
+    lib.ikg_rollout_params_default.restype = None
+    lib.ikg_control_rollout.argtypes = [vp, i32, vp, vp, vp, i64, C.POINTER(Bezier), C.POINTER(Bezier),
+                                        C.POINTER(RolloutParams), C.POINTER(RolloutOut), vp, C.c_uint32]
+    lib.ikg_control_rollout.restype = i32
     lib.ikg_model_specialize.argtypes = [vp, i32, i32, C.c_uint32]
     lib.ikg_model_specialize.restype = i32
     lib.ikg_model_is_specialized.argtypes = [vp, i32, i32]
@@ -283,6 +311,35 @@ def control_params(**gains) -> ControlParams:
             p.zero_tau_mask = int(v)
         else:
             raise ValueError(f"unknown controller parameter {k!r}")
+    return p
+
+
+def curve(traj):
+    """A trajectory -> (points [n, dim] float64 C-contiguous, t_min, t_max, mult):
+    an object with the reference Bezier's control_points_, T_min_, T_max_,
+    mult_T_, or a plain (points, t_min, t_max, mult) tuple."""
+    if hasattr(traj, "control_points_"):
+        traj = (traj.control_points_, traj.T_min_, traj.T_max_, traj.mult_T_)
+    pts, t_min, t_max, mult = traj
+    pts = np.ascontiguousarray(np.asarray(pts, dtype=np.float64))
+    if pts.ndim != 2:
+        raise ValueError(f"control points must be [n_points, dim], got {list(pts.shape)}")
+    return pts, float(t_min), float(t_max), float(mult)
+
+
+def bezier_desc(traj, dim=None):
+    """-> (ikg_bezier, the array it points into: keep it alive for the call)."""
+    pts, t_min, t_max, mult = curve(traj)
+    if dim is not None and pts.shape[1] != dim:
+        raise ValueError(f"control points have {pts.shape[1]} columns, the model has {dim} joints")
+    return Bezier(pts.ctypes.data, pts.shape[0], t_min, t_max, mult), pts
+
+
+def rollout_params(ticks, dt_sim=1e-3, dt_traj=1e-2, record_every=0, **gains) -> RolloutParams:
+    p = RolloutParams()
+    load().ikg_rollout_params_default(C.byref(p))
+    p.control = control_params(**gains)
+    p.dt_sim, p.dt_traj, p.ticks, p.record_every = float(dt_sim), float(dt_traj), int(ticks), int(record_every)
     return p
 
 

@@ -21,10 +21,18 @@ for many states in one launch of `ikg_dynamics_batch`, and
 `control_torques_batch` the whole second half of the law (:284-406: the
 operational-space inertia, the unconstrained QP and the torque line) through
 `ikg_control_torque_batch`.  `controllaw` is the drop-in for the reference
-function.  Only the simulator stays out of scope.  There is no CPU path: without the HIP library
-these raise `NativeLibraryError`.
+function.  `rollout` runs B closed loops of that law against a free-space
+rigid-body plant in one call of `ikg_control_rollout` (desired state from the
+Bezier curves, torque law, forward dynamics, semi-implicit Euler), and
+`Simulation` is the same plant one tick at a time behind the simulator's
+interface, so the reference's loop (control.py:461-463) runs without PyBullet.
+Contact, the cube, joint limits and joint damping stay out of scope
+(DESIGN.md §7).  There is no CPU path: without the HIP library these raise
+`NativeLibraryError`.
 """
 from __future__ import annotations
+
+import json
 
 import numpy as np
 
@@ -94,3 +102,93 @@ def controllaw(sim, robot, trajs, tcurrent, cube):
     q_des, vq_des = trajs[0](tcurrent), trajs[1](tcurrent)  # :269-270
     tau = robot.solver.control_torques(row(q), row(vq), row(q_des), row(vq_des), outputs=("tau",))["tau"][0]
     sim.step(tau.tolist())  # :410
+
+
+# ---------------------------------------------------------------- closed loop (control.py:415-463)
+class Curve:
+    """A Bezier curve with the reference class's attributes (control_points_,
+    T_min_, T_max_, mult_T_) and call semantics (control.py:18-46).  Calling it
+    evaluates ONE time on the host, for the per-tick drop-in `controllaw`;
+    batches go through `IKSolver.bezier` / `rollout`."""
+
+    def __init__(self, pointlist, t_min=0.0, t_max=1.0, mult_t=1.0):
+        self.control_points_ = [np.asarray(p, dtype=np.float64) for p in pointlist]
+        self.T_min_, self.T_max_, self.mult_T_ = float(t_min), float(t_max), float(mult_t)
+        self.degree_ = len(self.control_points_) - 1
+        if self.degree_ < 1 or self.T_max_ <= self.T_min_:
+            raise ValueError("a curve needs two control points and t_max > t_min")
+
+    def __call__(self, t):
+        if not (self.T_min_ <= t <= self.T_max_):
+            raise ValueError("time out of the curve's range")
+        P = self.control_points_
+        if self.degree_ == 1:
+            return self.mult_T_ * P[0]
+        u = (t - self.T_min_) / (self.T_max_ - self.T_min_)
+        uo, bc, tn = 1.0 - u, 1.0, 1.0
+        tmp = P[0] * uo
+        for i in range(1, self.degree_):
+            tn *= u
+            bc *= (self.degree_ - i + 1) / i
+            tmp = (tmp + (tn * bc) * P[i]) * uo
+        return (tmp + (tn * u) * P[-1]) * self.mult_T_
+
+    def derivative(self, order=1):
+        """Bezier.derivative: control points degree (P[i+1] - P[i]), mult * (1 / (t_max - t_min))."""
+        c = self
+        for _ in range(order):
+            P = c.control_points_
+            pts = [c.degree_ * (b - a) for a, b in zip(P[:-1], P[1:])]
+            if len(pts) < 2:
+                pts = pts + pts  # a constant: two equal points evaluate to mult P0
+            c = Curve(pts, c.T_min_, c.T_max_, c.mult_T_ * (1.0 / (c.T_max_ - c.T_min_)))
+        return c
+
+
+def load_trajectory(path):
+    """The reference's trajectory file (save_trajectory_to_json: q_, vq_,
+    vvq_control_points, t_min, t_max, mult_t) -> (q_of_t, vq_of_t, vvq_of_t).
+    As load_trajectory_from_json does, EVERY curve gets the file's mult_t, so a
+    file-loaded velocity curve is the unscaled derivative (the 1 / (t_max -
+    t_min) of Bezier.derivative is not stored); `q_of_t.derivative(1)` gives the
+    scaled one."""
+    with open(path) as f:
+        d = json.load(f)
+    return tuple(Curve(d[k], d["t_min"], d["t_max"], d["mult_t"])
+                 for k in ("q_control_points", "vq_control_points", "vvq_control_points"))
+
+
+def rollout(robot, q0, vq0, trajs, t0=None, ticks=1500, **kw):
+    """B closed loops of `controllaw` against the free rigid-body plant in one
+    call (`IKSolver.rollout`, GPU, fp64): trajs = (q_of_t, vq_of_t[, ...]) as
+    the reference passes them; dt_sim, dt_traj, record_every, outputs and the
+    gains as keywords.  1,500 ticks are the reference's 15 s run."""
+    return robot.solver.rollout(q0, vq0, (trajs[0], trajs[1]), t0=t0, ticks=ticks, **kw)
+
+
+class Simulation:
+    """The simulator's interface (getpybulletstate / setqsim / step) over the
+    free rigid-body plant: `step(torques)` is one B = 1 call of
+    `ikg_forward_dynamics_batch` and a semi-implicit Euler update (v += dt qdd,
+    q += dt v: Bullet's scheme), so the reference's loop
+        while tcur < total_time: controllaw(sim, robot, trajs, tcur, cube); tcur += DT
+    runs unmodified.  No contact, cube, joint limits or damping."""
+
+    def __init__(self, robot, dt=1e-3):
+        self.solver = robot.solver if hasattr(robot, "solver") else robot
+        self.dt = float(dt)
+        self.q = np.zeros(self.solver.nq)
+        self.v = np.zeros(self.solver.nq)
+
+    def setqsim(self, q, v=None):
+        self.q = np.array(q, dtype=np.float64).reshape(-1)
+        self.v = np.zeros_like(self.q) if v is None else np.array(v, dtype=np.float64).reshape(-1)
+
+    def getpybulletstate(self):
+        return self.q.copy(), self.v.copy()
+
+    def step(self, torques):
+        tau = np.asarray(torques, dtype=np.float64).reshape(1, -1)
+        qdd = self.solver.forward_dynamics(self.q.reshape(1, -1), self.v.reshape(1, -1), tau)[0]
+        self.v = self.v + self.dt * qdd
+        self.q = self.q + self.dt * self.v

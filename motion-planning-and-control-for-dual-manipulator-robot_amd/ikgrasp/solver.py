@@ -481,3 +481,95 @@ class IKSolver:
         _lib.check(self.lib.ikg_control_torque_batch(self._h, device, *[ptr(x) for x in arrs], B, C.byref(prm),
                                                      C.byref(out), s, flags))
         return res
+
+    # ------------------------------------------------------------------ forward dynamics, curves, closed-loop rollout
+    def _f64_io(self, first, stream):
+        """(prep, empty, ptr, stream, device, flags) for float64 numpy arrays or ROCm torch tensors."""
+        if _is_torch(first):
+            import torch
+            if not first.is_cuda or first.dtype != torch.float64:
+                raise ValueError("torch inputs must be float64 tensors on a ROCm device (or pass numpy arrays)")
+            dev = first.device
+            prep = lambda x, w: None if x is None else x.to(device=dev, dtype=torch.float64).contiguous().view(-1, w)
+            empty = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+            ptr = lambda x: None if x is None else x.data_ptr()
+            s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+            return prep, empty, ptr, s, dev.index or 0, 0
+        prep = lambda x, w: None if x is None else np.ascontiguousarray(x, dtype=np.float64).reshape(-1, w)
+        empty = lambda *shape: np.empty(shape, dtype=np.float64)
+        ptr = lambda x: None if x is None else x.ctypes.data
+        return prep, empty, ptr, None, self.device, _lib.IKG_FLAG_HOST_POINTERS
+
+    def forward_dynamics(self, q, v, tau, stream=None):
+        """ikg_forward_dynamics_batch (fp64): qdd [B,nq] = M(q)^-1 (tau - nle(q, v)),
+        pin.aba.  q, v, tau [B,nq] (numpy, or float64 torch tensors on a ROCm
+        device; v None = zero).  Needs `set_inertia`."""
+        nq = self.nq
+        prep, empty, ptr, s, device, flags = self._f64_io(q, stream)
+        qq, vv, tt = prep(q, nq), prep(v, nq), prep(tau, nq)
+        B = qq.shape[0]
+        for name, x in (("v", vv), ("tau", tt)):
+            if x is not None and x.shape[0] != B:
+                raise ValueError(f"{name} has {x.shape[0]} rows, q has {B}")
+        if tt is None:
+            raise ValueError("tau is required")
+        out = empty(B, nq)
+        _lib.check(self.lib.ikg_forward_dynamics_batch(self._h, device, ptr(qq), ptr(vv), ptr(tt), B, ptr(out), s,
+                                                       flags))
+        return out
+
+    def bezier(self, points, t_min, t_max, mult, times, stream=None):
+        """ikg_bezier_eval_batch: the reference's Bezier(points, t_min, t_max,
+        mult)(t) for every t of `times` [K] -> [K, dim].  points [n, dim] is a
+        host array; times numpy or a float64 ROCm tensor.  A time outside
+        [t_min, t_max] raises for numpy times, as the reference does."""
+        pts, t_min, t_max, mult = _lib.curve((points, t_min, t_max, mult))
+        prep, empty, ptr, s, device, flags = self._f64_io(times, stream)
+        tt = prep(times, 1)
+        K = tt.shape[0]
+        out = empty(K, pts.shape[1])
+        _lib.check(self.lib.ikg_bezier_eval_batch(device, pts.ctypes.data, pts.shape[0], pts.shape[1], t_min, t_max,
+                                                  mult, ptr(tt), K, ptr(out), s, flags))
+        return out
+
+    ROLLOUT_OUTPUTS = ("q", "v", "t", "q_hist", "v_hist", "tau_hist")
+
+    def rollout(self, q0, v0, trajs, t0=None, ticks=0, dt_sim=1e-3, dt_traj=1e-2, record_every=0,
+                outputs=("q", "v", "t"), stream=None, **gains) -> dict:
+        """ikg_control_rollout (fp64): `ticks` closed-loop ticks of B states in
+        one call: desired state from the curves, the torque law, forward
+        dynamics, semi-implicit Euler, clock.  The plant is the free rigid-body
+        tree (no contact, cube, joint limits or damping).
+        q0, v0 [B,nq] (numpy or float64 ROCm tensors, never written; v0 None =
+        zero); t0 [B] or None = the q curve's t_min.  trajs = (q curve, v curve),
+        each an object with the reference Bezier's control_points_, T_min_,
+        T_max_, mult_T_ or a (points, t_min, t_max, mult) tuple.  dt_traj: the
+        trajectory clock's step per tick (the reference's DT = 0.01 per 1 ms
+        tick).  outputs: final q, v [B,nq], t [B]; with record_every > 0
+        q_hist, v_hist, tau_hist [B, ticks // record_every, nq].
+        `gains` as control_torques."""
+        unknown = set(outputs) - set(self.ROLLOUT_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        nq = self.nq
+        bq, keep_q = _lib.bezier_desc(trajs[0], nq)
+        bv, keep_v = _lib.bezier_desc(trajs[1], nq)
+        prm = _lib.rollout_params(ticks, dt_sim, dt_traj, record_every, **gains)
+        prep, empty, ptr, s, device, flags = self._f64_io(q0, stream)
+        qq, vv = prep(q0, nq), prep(v0, nq)
+        tt = None if t0 is None else prep(t0, 1)
+        B = qq.shape[0]
+        if vv is not None and vv.shape[0] != B:
+            raise ValueError(f"v0 has {vv.shape[0]} rows, q0 has {B}")
+        if tt is not None and tt.shape[0] != B:
+            raise ValueError(f"t0 has {tt.shape[0]} entries, q0 has {B} rows")
+        R = int(ticks) // int(record_every) if record_every else 0
+        if not R and any(k.endswith("_hist") for k in outputs):
+            raise ValueError("history outputs need record_every > 0 and ticks >= record_every")
+        shape = lambda k: (B,) if k == "t" else ((B, R, nq) if k.endswith("_hist") else (B, nq))
+        res = {k: empty(*shape(k)) for k in outputs}
+        out = _lib.RolloutOut(*[ptr(res.get(k)) for k in self.ROLLOUT_OUTPUTS])
+        _lib.check(self.lib.ikg_control_rollout(self._h, device, ptr(qq), ptr(vv), ptr(tt), B, C.byref(bq), C.byref(bv),
+                                                C.byref(prm), C.byref(out), s, flags))
+        del keep_q, keep_v
+        return res
