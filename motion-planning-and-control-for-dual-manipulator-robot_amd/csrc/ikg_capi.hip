@@ -36,28 +36,68 @@ int hip_fail(hipError_t e, const char* what) {
   return fail(IKG_EHIP, "%s: %s", what, hipGetErrorString(e));
 }
 
+void free_slots(std::vector<void*>& slot) {
+  for (size_t i = 0; i < slot.size(); ++i)
+    if (slot[i]) {
+      (void)hipSetDevice((int)i);
+      (void)hipFree(slot[i]);
+      slot[i] = nullptr;
+    }
+}
+
+// One kind of table a model carries (joint tree, collision scene, inertias):
+// the fp64 and fp32 host tables and their uploads, one slot per device.
+template <template <typename> class K>
+struct Tables {
+  const char* missing;  // the error of a query before the tables were attached
+  bool present = false;
+  K<double> k64;
+  K<float> k32;
+  std::vector<void*> dev64, dev32;
+
+  // Upload to `device` once (under the model's lock); the slot is reused after.
+  template <typename T>
+  int get(std::mutex& mu, int device, const K<T>** out) {
+    if (!present) return fail(IKG_EINVAL, "%s", missing);
+    constexpr bool d = sizeof(T) == 8;
+    std::vector<void*>& slot = d ? dev64 : dev32;
+    const void* src = d ? (const void*)&k64 : (const void*)&k32;
+    std::lock_guard<std::mutex> lock(mu);
+    if ((int)slot.size() <= device) slot.resize(device + 1, nullptr);
+    if (!slot[device]) {
+      void* p = nullptr;
+      hipError_t e = hipMalloc(&p, sizeof(K<T>));
+      if (e != hipSuccess) return fail(IKG_ENOMEM, "hipMalloc(model tables): %s", hipGetErrorString(e));
+      e = hipMemcpy(p, src, sizeof(K<T>), hipMemcpyHostToDevice);
+      if (e != hipSuccess) {
+        (void)hipFree(p);
+        return hip_fail(e, "hipMemcpy(model tables)");
+      }
+      slot[device] = p;
+    }
+    *out = (const K<T>*)slot[device];
+    return IKG_OK;
+  }
+
+  // free the uploads (they are made again lazily); callers must not race a launch
+  void reset() {
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    free_slots(dev64);
+    free_slots(dev32);
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
 }  // namespace
 
 struct ikg_model {
   ikg_model_desc desc;
-  ikg::KModel<double> k64;
-  ikg::KModel<float> k32;
   int spec = ikg::kSpecGeneric;
   std::mutex mu;
-  std::vector<void*> dev64;  // per device
-  std::vector<void*> dev32;
-  // collision scene (ikg_model_set_collision)
-  bool has_collision = false;
-  ikg::KCollision<double> c64;
-  ikg::KCollision<float> c32;
-  std::vector<void*> col64;
-  std::vector<void*> col32;
-  // body inertias and gravity (ikg_model_set_inertia)
-  bool has_inertia = false;
-  ikg::KInertia<double> i64;
-  ikg::KInertia<float> i32;
-  std::vector<void*> ine64;
-  std::vector<void*> ine32;
+  Tables<ikg::KModel> kin{"", true};
+  Tables<ikg::KCollision> col{"no collision scene attached (ikg_model_set_collision)"};
+  Tables<ikg::KInertia> ine{"no body inertias attached (ikg_model_set_inertia)"};
   // model-specialised pair kernels (ikg_model_specialize): code objects per
   // dtype (0 = f64, 1 = f32), loaded modules per device
   std::vector<char> jit_code[2];
@@ -70,48 +110,6 @@ struct ikg_model {
     std::lock_guard<std::mutex> lock(mu);
     const auto& v = jit[sizeof(T) == 8 ? 0 : 1];
     return device < (int)v.size() ? v[device] : nullptr;
-  }
-
-  // Upload `bytes` of `src` to `slot[device]` once; the slot is reused after.
-  int upload(std::vector<void*>& slot, int device, const void* src, size_t bytes, const void** out) {
-    std::lock_guard<std::mutex> lock(mu);
-    if ((int)slot.size() <= device) slot.resize(device + 1, nullptr);
-    if (!slot[device]) {
-      void* p = nullptr;
-      hipError_t e = hipMalloc(&p, bytes);
-      if (e != hipSuccess) return fail(IKG_ENOMEM, "hipMalloc(model tables): %s", hipGetErrorString(e));
-      e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
-      if (e != hipSuccess) {
-        (void)hipFree(p);
-        return hip_fail(e, "hipMemcpy(model tables)");
-      }
-      slot[device] = p;
-    }
-    *out = slot[device];
-    return IKG_OK;
-  }
-
-  template <typename T>
-  int device_tables(int device, const ikg::KModel<T>** out) {
-    const bool d = sizeof(T) == 8;
-    return upload(d ? dev64 : dev32, device, d ? (const void*)&k64 : (const void*)&k32, sizeof(ikg::KModel<T>),
-                  (const void**)out);
-  }
-
-  template <typename T>
-  int collision_tables(int device, const ikg::KCollision<T>** out) {
-    if (!has_collision) return fail(IKG_EINVAL, "no collision scene attached (ikg_model_set_collision)");
-    const bool d = sizeof(T) == 8;
-    return upload(d ? col64 : col32, device, d ? (const void*)&c64 : (const void*)&c32, sizeof(ikg::KCollision<T>),
-                  (const void**)out);
-  }
-
-  template <typename T>
-  int inertia_tables(int device, const ikg::KInertia<T>** out) {
-    if (!has_inertia) return fail(IKG_EINVAL, "no body inertias attached (ikg_model_set_inertia)");
-    const bool d = sizeof(T) == 8;
-    return upload(d ? ine64 : ine32, device, d ? (const void*)&i64 : (const void*)&i32, sizeof(ikg::KInertia<T>),
-                  (const void**)out);
   }
 };
 
@@ -141,32 +139,24 @@ struct DeviceGuard {
   }
 };
 
-// Stages host buffers through device scratch when IKG_FLAG_HOST_POINTERS is set.
+// The pointers of one call.  With IKG_FLAG_HOST_POINTERS every input and output
+// is staged through device scratch that lives until the call returns; without
+// it in() and out() hand the caller's device pointers through.
 struct Staging {
+  struct Out {
+    void *host, *dev;
+    size_t bytes;
+  };
   std::vector<void*> allocs;
+  std::vector<Out> outs;
   hipStream_t s;
+  bool host;
   int rc = IKG_OK;
-  explicit Staging(hipStream_t st) : s(st) {}
+  Staging(hipStream_t st, uint32_t flags) : s(st), host(flags & IKG_FLAG_HOST_POINTERS) {}
   ~Staging() {
     for (void* p : allocs) (void)hipFree(p);
   }
-  void* in(const void* host, size_t bytes) {
-    if (!host || rc) return nullptr;
-    void* d = nullptr;
-    hipError_t e = hipMalloc(&d, bytes ? bytes : 1);
-    if (e != hipSuccess) {
-      rc = fail(IKG_ENOMEM, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
-      return nullptr;
-    }
-    allocs.push_back(d);
-    if (bytes) {
-      e = hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, s);
-      if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync(H2D)");
-    }
-    return d;
-  }
-  void* out(size_t bytes) { return in_alloc(bytes); }
-  void* in_alloc(size_t bytes) {
+  void* alloc(size_t bytes) {
     if (rc) return nullptr;
     void* d = nullptr;
     hipError_t e = hipMalloc(&d, bytes ? bytes : 1);
@@ -177,22 +167,40 @@ struct Staging {
     allocs.push_back(d);
     return d;
   }
-  int back(void* host, const void* dev, size_t bytes) {
-    if (!host || !dev || rc) return rc;
-    hipError_t e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s);
-    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync(D2H)");
-    return rc;
+  // a device copy of a host array, whatever the flag (the small tables of a call)
+  void* upload(const void* p, size_t bytes) {
+    void* d = p ? alloc(bytes) : nullptr;
+    if (d && bytes) {
+      const hipError_t e = hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, s);
+      if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync(H2D)");
+    }
+    return d;
+  }
+  const void* in(const void* p, size_t bytes) { return host ? upload(p, bytes) : p; }
+  // an optional output: the device buffer the kernels write; finish() copies it back
+  void* out(void* p, size_t bytes) {
+    if (!host || !p) return p;
+    void* d = alloc(bytes);
+    outs.push_back({p, d, bytes});
+    return d;
+  }
+  // The end of a call whose launches are queued: copy the staged outputs back
+  // and wait for them.  `sync`: wait although the call passed device pointers
+  // (scratch of this object is still in use by the queued kernels).
+  int finish(bool sync = false) {
+    for (const Out& o : outs) {
+      if (!o.dev || rc) break;
+      const hipError_t e = hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, s);
+      if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync(D2H)");
+    }
+    if (rc) return rc;
+    if (host || sync) {
+      const hipError_t e = hipStreamSynchronize(s);
+      if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+    }
+    return IKG_OK;
   }
 };
-
-void free_slots(std::vector<void*>& slot) {
-  for (size_t i = 0; i < slot.size(); ++i)
-    if (slot[i]) {
-      (void)hipSetDevice((int)i);
-      (void)hipFree(slot[i]);
-      slot[i] = nullptr;
-    }
-}
 
 // Problems per wave.  Full 32-problem waves are fastest at every batch size
 // measured (B = 4k..131k, fp32/fp64): spreading a small batch over more,
@@ -231,9 +239,39 @@ int check_finite(const void* p, int64_t n, const char* what) {
   return IKG_OK;
 }
 
+// the [B, width] arrays of a host-pointer call, in the order given; a null (optional) array passes
+struct HostArray {
+  const void* p;
+  int64_t width;
+  const char* what;
+};
+template <typename T>
+int check_finite_rows(uint32_t flags, int64_t B, std::initializer_list<HostArray> rows) {
+  if (!(flags & IKG_FLAG_HOST_POINTERS)) return IKG_OK;
+  for (const HostArray& r : rows)
+    if (r.p)
+      if (int rc = check_finite<T>(r.p, B * r.width, r.what)) return rc;
+  return IKG_OK;
+}
+
+// f(T{}) for the element type of `dtype` (checked by the caller)
+template <typename F>
+int by_dtype(int dtype, F&& f) {
+  return dtype == IKG_F64 ? f(double{}) : f(float{});
+}
+
 template <typename T>
 ikg::KParams<T> kparams(const ikg_params* p) {
   return ikg::make_kparams<T>(p);
+}
+
+template <typename T>
+int check_variant(const ikg_model* model, const ikg_params* params) {
+  if (params->variant == IKG_VARIANT_PACKED && (sizeof(T) != 4 || model->spec != ikg::kSpecNextage || params->lambda > 0))
+    return fail(IKG_EINVAL, "variant PACKED needs fp32, a Nextage-class model and lambda = 0");
+  if (params->variant == IKG_VARIANT_QUAD && (model->spec != ikg::kSpecNextage || params->lambda > 0))
+    return fail(IKG_EINVAL, "variant QUAD needs a Nextage-class model and lambda = 0");
+  return IKG_OK;
 }
 
 // Records in the batch kernel for the collision continuation (the default
@@ -346,38 +384,36 @@ int solve_batch_t(ikg_model* model, int device, const void* targets, const void*
                   hipStream_t s, uint32_t flags) {
   if (!ikg::stream_capturing(s)) ikg::ws_drain(&model->ws);  // scratch of destroyed graphs
   const ikg::KModel<T>* dm = nullptr;
-  int rc = model->device_tables<T>(device, &dm);
+  int rc = model->kin.get<T>(model->mu, device, &dm);
   if (rc) return rc;
   const ikg::KCollision<T>* dc = nullptr;
-  if (params->check_collision && (rc = model->collision_tables<T>(device, &dc))) return rc;
+  if (params->check_collision && (rc = model->col.get<T>(model->mu, device, &dc))) return rc;
   const int nq = model->desc.nq;
-  ikg::BatchArgs a{targets, q0, q0_stride, B, q_out, converged, iters, err_out, 32};
-  a.ws_owner = &model->ws;
-  a.ppw = params->problems_per_wave > 0 ? params->problems_per_wave : auto_ppw(device, B);
-  a.variant = params->variant;
-  if (params->variant == IKG_VARIANT_PACKED && (sizeof(T) != 4 || model->spec != ikg::kSpecNextage || params->lambda > 0))
-    return fail(IKG_EINVAL, "variant PACKED needs fp32, a Nextage-class model and lambda = 0");
-  if (params->variant == IKG_VARIANT_QUAD && (model->spec != ikg::kSpecNextage || params->lambda > 0))
-    return fail(IKG_EINVAL, "variant QUAD needs a Nextage-class model and lambda = 0");
-  Staging st(s);
-  const bool host = flags & IKG_FLAG_HOST_POINTERS;
-  if (host) {
-    const int64_t q0_rows = q0_stride == 0 ? 1 : B;
+  if ((rc = check_variant<T>(model, params))) return rc;
+  Staging st(s, flags);
+  const int64_t q0_rows = q0_stride == 0 ? 1 : B;
+  if (st.host) {
     if ((rc = check_finite<T>(targets, 12 * B, "targets"))) return rc;
     for (int64_t r = 0; r < q0_rows; ++r)
       if ((rc = check_finite<T>(static_cast<const T*>(q0) + r * q0_stride, nq, "q0 row"))) return rc;
-    a.targets = st.in(targets, sizeof(T) * 12 * B);
-    a.q0 = st.in(q0, sizeof(T) * (q0_stride == 0 ? nq : q0_stride * (q0_rows - 1) + nq));
-    a.q_out = st.out(sizeof(T) * nq * B);
-    a.converged = converged ? (uint8_t*)st.out(B) : nullptr;
-    a.iters = iters ? (int32_t*)st.out(sizeof(int32_t) * B) : nullptr;
-    a.err_out = err_out ? st.out(sizeof(T) * 2 * B) : nullptr;
-    if (st.rc) return st.rc;
   }
+  ikg::BatchArgs a{st.in(targets, sizeof(T) * 12 * B),
+                   st.in(q0, sizeof(T) * (q0_stride * (q0_rows - 1) + nq)),
+                   q0_stride,
+                   B,
+                   st.out(q_out, sizeof(T) * nq * B),
+                   (uint8_t*)st.out(converged, B),
+                   (int32_t*)st.out(iters, sizeof(int32_t) * B),
+                   st.out(err_out, sizeof(T) * 2 * B),
+                   32};
+  if (st.rc) return st.rc;
+  a.ws_owner = &model->ws;
+  a.ppw = params->problems_per_wave > 0 ? params->problems_per_wave : auto_ppw(device, B);
+  a.variant = params->variant;
   if (dc) {  // the continuation reads and rewrites every per-problem output
-    if (!a.converged) a.converged = (uint8_t*)st.out(B);
-    if (!a.iters) a.iters = (int32_t*)st.out(sizeof(int32_t) * B);
-    if (!a.err_out) a.err_out = st.out(sizeof(T) * 2 * B);
+    if (!a.converged) a.converged = (uint8_t*)st.alloc(B);
+    if (!a.iters) a.iters = (int32_t*)st.alloc(sizeof(int32_t) * B);
+    if (!a.err_out) a.err_out = st.alloc(sizeof(T) * 2 * B);
     if (st.rc) return st.rc;
   }
   a.jit = model->jit_kernels<T>(device);
@@ -408,7 +444,7 @@ int solve_batch_t(ikg_model* model, int device, const void* targets, const void*
       }
       return hip_fail(e, "ikg pair kernel launch");
     }
-    if (dc) e = ikg::launch_collide_continue<T>(dm, dc, kp, c, model->spec, nq, model->c64.n_geoms, s);
+    if (dc) e = ikg::launch_collide_continue<T>(dm, dc, kp, c, model->spec, nq, model->col.k64.n_geoms, s);
   }
   if (rec) {
     ikg::ws_trace("free rec", rec, 0, s);
@@ -416,16 +452,7 @@ int solve_batch_t(ikg_model* model, int device, const void* targets, const void*
     if (e == hipSuccess) e = ef;
   }
   if (e != hipSuccess) return hip_fail(e, "ikg collision continuation launch");
-  if (host) {
-    st.back(q_out, a.q_out, sizeof(T) * nq * B);
-    st.back(converged, a.converged, B);
-    st.back(iters, a.iters, sizeof(int32_t) * B);
-    st.back(err_out, a.err_out, sizeof(T) * 2 * B);
-    if (st.rc) return st.rc;
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-  }
-  return IKG_OK;
+  return st.finish();
 }
 
 template <typename T>
@@ -434,37 +461,37 @@ int solve_multi_t(ikg_model* model, int device, const void* targets, int64_t T_,
                   int32_t* best_seed, hipStream_t s, uint32_t flags) {
   if (!ikg::stream_capturing(s)) ikg::ws_drain(&model->ws);  // scratch of destroyed graphs
   const ikg::KModel<T>* dm = nullptr;
-  int rc = model->device_tables<T>(device, &dm);
+  int rc = model->kin.get<T>(model->mu, device, &dm);
   if (rc) return rc;
   const int nq = model->desc.nq;
-  ikg::MultiArgs a{targets, T_, seeds, S, q_out, converged, iters, err_out, best_seed, nq,
-                   nullptr, nullptr, nullptr, nullptr};
+  if ((rc = check_variant<T>(model, params))) return rc;
+  const ikg::KCollision<T>* dc = nullptr;
+  if (params->check_collision && (rc = model->col.get<T>(model->mu, device, &dc))) return rc;
+  Staging st(s, flags);
+  if (st.host &&
+      ((rc = check_finite<T>(targets, 12 * T_, "targets")) || (rc = check_finite<T>(seeds, nq * S, "seeds"))))
+    return rc;
+  ikg::MultiArgs a{st.in(targets, sizeof(T) * 12 * T_),
+                   T_,
+                   st.in(seeds, sizeof(T) * nq * S),
+                   S,
+                   st.out(q_out, sizeof(T) * nq * T_),
+                   (uint8_t*)st.out(converged, T_),
+                   (int32_t*)st.out(iters, sizeof(int32_t) * T_),
+                   st.out(err_out, sizeof(T) * 2 * T_),
+                   (int32_t*)st.out(best_seed, sizeof(int32_t) * T_),
+                   nq,
+                   nullptr,
+                   nullptr,
+                   nullptr,
+                   nullptr};
+  if (st.rc) return st.rc;
   a.variant = params->variant;
   a.jit = model->jit_kernels<T>(device);
   a.ws_owner = &model->ws;
-  if (params->variant == IKG_VARIANT_PACKED && (sizeof(T) != 4 || model->spec != ikg::kSpecNextage || params->lambda > 0))
-    return fail(IKG_EINVAL, "variant PACKED needs fp32, a Nextage-class model and lambda = 0");
-  if (params->variant == IKG_VARIANT_QUAD && (model->spec != ikg::kSpecNextage || params->lambda > 0))
-    return fail(IKG_EINVAL, "variant QUAD needs a Nextage-class model and lambda = 0");
-  if (params->check_collision) {
-    const ikg::KCollision<T>* dc = nullptr;
-    if ((rc = model->collision_tables<T>(device, &dc))) return rc;
+  if (dc) {
     a.collision = dc;
-    a.n_geoms = model->c64.n_geoms;
-  }
-  Staging st(s);
-  const bool host = flags & IKG_FLAG_HOST_POINTERS;
-  if (host) {
-    if ((rc = check_finite<T>(targets, 12 * T_, "targets")) || (rc = check_finite<T>(seeds, nq * S, "seeds")))
-      return rc;
-    a.targets = st.in(targets, sizeof(T) * 12 * T_);
-    a.seeds = st.in(seeds, sizeof(T) * nq * S);
-    a.q_out = st.out(sizeof(T) * nq * T_);
-    a.converged = converged ? (uint8_t*)st.out(T_) : nullptr;
-    a.iters = iters ? (int32_t*)st.out(sizeof(int32_t) * T_) : nullptr;
-    a.err_out = err_out ? st.out(sizeof(T) * 2 * T_) : nullptr;
-    a.best_seed = best_seed ? (int32_t*)st.out(sizeof(int32_t) * T_) : nullptr;
-    if (st.rc) return st.rc;
+    a.n_geoms = model->col.k64.n_geoms;
   }
   // per-seed workspace, stream-ordered (capturable) allocation
   const int64_t n = T_ * S;
@@ -505,43 +532,21 @@ int solve_multi_t(ikg_model* model, int device, const void* targets, int64_t T_,
   hipError_t e2 = ikg::ws_free(&model->ws, ws, s);
   if (e != hipSuccess) return hip_fail(e, "ikg multistart kernel launch");
   if (e2 != hipSuccess) return hip_fail(e2, "multistart workspace free");
-  if (host) {
-    st.back(q_out, a.q_out, sizeof(T) * nq * T_);
-    st.back(converged, a.converged, T_);
-    st.back(iters, a.iters, sizeof(int32_t) * T_);
-    st.back(err_out, a.err_out, sizeof(T) * 2 * T_);
-    st.back(best_seed, a.best_seed, sizeof(int32_t) * T_);
-    if (st.rc) return st.rc;
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-  }
-  return IKG_OK;
+  return st.finish();
 }
 
 template <typename T>
 int fk_t(ikg_model* model, int device, const void* q, int64_t B, void* hands, hipStream_t s, uint32_t flags) {
   const ikg::KModel<T>* dm = nullptr;
-  int rc = model->device_tables<T>(device, &dm);
+  int rc = model->kin.get<T>(model->mu, device, &dm);
   if (rc) return rc;
-  const int nq = model->desc.nq;
-  Staging st(s);
-  const bool host = flags & IKG_FLAG_HOST_POINTERS;
-  const void* dq = q;
-  void* dh = hands;
-  if (host) {
-    dq = st.in(q, sizeof(T) * nq * B);
-    dh = st.out(sizeof(T) * 24 * B);
-    if (st.rc) return st.rc;
-  }
+  Staging st(s, flags);
+  const void* dq = st.in(q, sizeof(T) * model->desc.nq * B);
+  void* dh = st.out(hands, sizeof(T) * 24 * B);
+  if (st.rc) return st.rc;
   hipError_t e = ikg::launch_fk<T>(dm, dq, B, dh, s);
   if (e != hipSuccess) return hip_fail(e, "ikg fk kernel launch");
-  if (host) {
-    st.back(hands, dh, sizeof(T) * 24 * B);
-    if (st.rc) return st.rc;
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-  }
-  return IKG_OK;
+  return st.finish();
 }
 
 template <typename T>
@@ -549,69 +554,42 @@ int collision_t(ikg_model* model, int device, const void* q, const void* targets
                 hipStream_t s, uint32_t flags) {
   const ikg::KModel<T>* dm = nullptr;
   const ikg::KCollision<T>* dc = nullptr;
-  int rc = model->device_tables<T>(device, &dm);
-  if (rc || (rc = model->collision_tables<T>(device, &dc))) return rc;
-  const int nq = model->desc.nq;
-  Staging st(s);
-  const bool host = flags & IKG_FLAG_HOST_POINTERS;
-  const void* dq = q;
-  const void* dt = targets;
-  uint8_t* dout = out;
-  if (host) {
-    dq = st.in(q, sizeof(T) * nq * B);
-    dt = st.in(targets, sizeof(T) * 12 * B);
-    dout = (uint8_t*)st.out(B);
-    if (st.rc) return st.rc;
-  }
+  int rc = model->kin.get<T>(model->mu, device, &dm);
+  if (rc || (rc = model->col.get<T>(model->mu, device, &dc))) return rc;
+  Staging st(s, flags);
+  const void* dq = st.in(q, sizeof(T) * model->desc.nq * B);
+  const void* dt = st.in(targets, sizeof(T) * 12 * B);
+  uint8_t* dout = (uint8_t*)st.out(out, B);
+  if (st.rc) return st.rc;
   hipError_t e = ikg::launch_collision<T>(dm, dc, dq, dt, B, dout, s);
   if (e != hipSuccess) return hip_fail(e, "ikg collision kernel launch");
-  if (host) {
-    st.back(out, dout, B);
-    if (st.rc) return st.rc;
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-  }
-  return IKG_OK;
+  return st.finish();
 }
 
 template <typename T>
 int log6_t(const void* M, int64_t B, void* out, hipStream_t s, uint32_t flags) {
-  Staging st(s);
-  const bool host = flags & IKG_FLAG_HOST_POINTERS;
-  const void* dm = M;
-  void* dout = out;
-  if (host) {
-    dm = st.in(M, sizeof(T) * 12 * B);
-    dout = st.out(sizeof(T) * 6 * B);
-    if (st.rc) return st.rc;
-  }
+  Staging st(s, flags);
+  const void* dm = st.in(M, sizeof(T) * 12 * B);
+  void* dout = st.out(out, sizeof(T) * 6 * B);
+  if (st.rc) return st.rc;
   hipError_t e = ikg::launch_log6<T>(dm, B, dout, s);
   if (e != hipSuccess) return hip_fail(e, "ikg log6 kernel launch");
-  if (host) {
-    st.back(out, dout, sizeof(T) * 6 * B);
-    if (st.rc) return st.rc;
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-  }
-  return IKG_OK;
+  return st.finish();
 }
 
 template <typename T>
 int pair_state_t(ikg_model* model, int device, const void* targets, const void* q0, int64_t B, void* out) {
   const ikg::KModel<T>* dm = nullptr;
-  int rc = model->device_tables<T>(device, &dm);
+  int rc = model->kin.get<T>(model->mu, device, &dm);
   if (rc) return rc;
-  Staging st(0);
+  Staging st(0, IKG_FLAG_HOST_POINTERS);
   const void* dt = st.in(targets, sizeof(T) * 12 * B);
   const void* dq = st.in(q0, sizeof(T) * model->desc.nq);
-  void* dout = st.out(sizeof(T) * 62 * B);
+  void* dout = st.out(out, sizeof(T) * 62 * B);
   if (st.rc) return st.rc;
   hipError_t e = ikg::launch_pair_state<T>(dm, dt, dq, 0, B, dout, 0);
   if (e != hipSuccess) return hip_fail(e, "pair state kernel");
-  st.back(out, dout, sizeof(T) * 62 * B);
-  if (st.rc) return st.rc;
-  e = hipStreamSynchronize(0);
-  return e == hipSuccess ? IKG_OK : hip_fail(e, "hipStreamSynchronize");
+  return st.finish();
 }
 
 }  // namespace
@@ -627,8 +605,7 @@ int ikg_debug_pair_state(const ikg_model* model, int device, int dtype, const vo
   DeviceGuard g(device);
   if (g.rc) return g.rc;
   ikg_model* m = const_cast<ikg_model*>(model);
-  return dtype == IKG_F64 ? pair_state_t<double>(m, device, targets, q0, B, out)
-                          : pair_state_t<float>(m, device, targets, q0, B, out);
+  return by_dtype(dtype, [&](auto t) { return pair_state_t<decltype(t)>(m, device, targets, q0, B, out); });
 }
 
 int ikg_log6_batch(int device, int dtype, const void* M, int64_t B, void* out, void* stream, uint32_t flags) {
@@ -640,7 +617,7 @@ int ikg_log6_batch(int device, int dtype, const void* M, int64_t B, void* out, v
   if (g.rc) return g.rc;
   if (B == 0) return IKG_OK;
   hipStream_t s = (hipStream_t)stream;
-  return dtype == IKG_F64 ? log6_t<double>(M, B, out, s, flags) : log6_t<float>(M, B, out, s, flags);
+  return by_dtype(dtype, [&](auto t) { return log6_t<decltype(t)>(M, B, out, s, flags); });
 }
 
 const char* ikg_last_error(void) { return g_err; }
@@ -719,9 +696,9 @@ int ikg_model_create(const ikg_model_desc* d, ikg_model** out) {
   ikg_model* m = new (std::nothrow) ikg_model();
   if (!m) return fail(IKG_ENOMEM, "out of host memory");
   m->desc = *d;
-  ikg::build_kmodel<double>(*d, m->k64);
-  ikg::build_kmodel<float>(*d, m->k32);
-  m->spec = ikg::choose_spec(m->k64);
+  ikg::build_kmodel<double>(*d, m->kin.k64);
+  ikg::build_kmodel<float>(*d, m->kin.k32);
+  m->spec = ikg::choose_spec(m->kin.k64);
   *out = m;
   return IKG_OK;
 }
@@ -730,12 +707,9 @@ void ikg_model_destroy(ikg_model* m) {
   if (!m) return;
   int prev = -1;
   (void)hipGetDevice(&prev);
-  free_slots(m->dev64);
-  free_slots(m->dev32);
-  free_slots(m->col64);
-  free_slots(m->col32);
-  free_slots(m->ine64);
-  free_slots(m->ine32);
+  m->kin.reset();
+  m->col.reset();
+  m->ine.reset();
   for (auto& v : m->jit)
     for (size_t i = 0; i < v.size(); ++i)
       if (v[i]) {
@@ -785,10 +759,10 @@ int ikg_solve_batch(const ikg_model* model, int device, int dtype, const void* t
   if (B == 0) return IKG_OK;
   ikg_model* m = const_cast<ikg_model*>(model);
   hipStream_t s = (hipStream_t)stream;
-  return dtype == IKG_F64 ? solve_batch_t<double>(m, device, targets, q0, q0_stride, B, params, q_out, converged,
-                                                  iters, err_out, s, flags)
-                          : solve_batch_t<float>(m, device, targets, q0, q0_stride, B, params, q_out, converged,
-                                                 iters, err_out, s, flags);
+  return by_dtype(dtype, [&](auto t) {
+    return solve_batch_t<decltype(t)>(m, device, targets, q0, q0_stride, B, params, q_out, converged, iters, err_out, s,
+                                      flags);
+  });
 }
 
 int ikg_solve_multistart(const ikg_model* model, int device, int dtype, const void* targets, int64_t T,
@@ -811,10 +785,10 @@ int ikg_solve_multistart(const ikg_model* model, int device, int dtype, const vo
   if (T == 0) return IKG_OK;
   ikg_model* m = const_cast<ikg_model*>(model);
   hipStream_t s = (hipStream_t)stream;
-  return dtype == IKG_F64 ? solve_multi_t<double>(m, device, targets, T, seeds, S, params, q_out, converged, iters,
-                                                  err_out, best_seed, s, flags)
-                          : solve_multi_t<float>(m, device, targets, T, seeds, S, params, q_out, converged, iters,
-                                                 err_out, best_seed, s, flags);
+  return by_dtype(dtype, [&](auto t) {
+    return solve_multi_t<decltype(t)>(m, device, targets, T, seeds, S, params, q_out, converged, iters, err_out,
+                                      best_seed, s, flags);
+  });
 }
 
 int ikg_fk_batch(const ikg_model* model, int device, int dtype, const void* q, int64_t B, void* hands, void* stream,
@@ -829,8 +803,7 @@ int ikg_fk_batch(const ikg_model* model, int device, int dtype, const void* q, i
   if (B == 0) return IKG_OK;
   ikg_model* m = const_cast<ikg_model*>(model);
   hipStream_t s = (hipStream_t)stream;
-  return dtype == IKG_F64 ? fk_t<double>(m, device, q, B, hands, s, flags)
-                          : fk_t<float>(m, device, q, B, hands, s, flags);
+  return by_dtype(dtype, [&](auto t) { return fk_t<decltype(t)>(m, device, q, B, hands, s, flags); });
 }
 
 int ikg_model_set_collision(ikg_model* m, const ikg_collision_desc* d) {
@@ -856,14 +829,10 @@ int ikg_model_set_collision(ikg_model* m, const ikg_collision_desc* d) {
       return fail(IKG_EINVAL, "pair %d: bad geometry indices (%d, %d)", k, a, b);
   }
   std::lock_guard<std::mutex> lock(m->mu);
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  free_slots(m->col64);  // re-uploaded lazily; callers must not race a solve
-  free_slots(m->col32);
-  if (prev >= 0) (void)hipSetDevice(prev);
-  ikg::build_kcollision<double>(*d, m->c64);
-  ikg::build_kcollision<float>(*d, m->c32);
-  m->has_collision = true;
+  m->col.reset();
+  ikg::build_kcollision<double>(*d, m->col.k64);
+  ikg::build_kcollision<float>(*d, m->col.k32);
+  m->col.present = true;
   return IKG_OK;
 }
 
@@ -874,15 +843,16 @@ int ikg_collision_batch(const ikg_model* model, int device, int dtype, const voi
   if (B < 0) return fail(IKG_EINVAL, "B must be >= 0");
   if (B > 0 && (!q || !targets || !in_collision)) return fail(IKG_EINVAL, "q, targets and in_collision are required");
   if (dtype != IKG_F64 && dtype != IKG_F32) return fail(IKG_EINVAL, "dtype %d unknown", dtype);
-  if (!model->has_collision) return fail(IKG_EINVAL, "no collision scene attached (ikg_model_set_collision)");
+  if (!model->col.present) return fail(IKG_EINVAL, "%s", model->col.missing);
   if (B > kMaxWaves) return fail(IKG_EINVAL, "B=%lld too large for one launch (at most %lld)", (long long)B, (long long)kMaxWaves);
   DeviceGuard g(device);
   if (g.rc) return g.rc;
   if (B == 0) return IKG_OK;
   ikg_model* m = const_cast<ikg_model*>(model);
   hipStream_t s = (hipStream_t)stream;
-  return dtype == IKG_F64 ? collision_t<double>(m, device, q, targets, B, in_collision, s, flags)
-                          : collision_t<float>(m, device, q, targets, B, in_collision, s, flags);
+  return by_dtype(dtype, [&](auto t) {
+    return collision_t<decltype(t)>(m, device, q, targets, B, in_collision, s, flags);
+  });
 }
 
 }  // extern "C"
@@ -893,53 +863,33 @@ int distance_t(ikg_model* model, int device, const void* q, const void* targets,
                int32_t n, void* out, hipStream_t s, uint32_t flags) {
   const ikg::KModel<T>* dm = nullptr;
   const ikg::KCollision<T>* dc = nullptr;
-  int rc = model->device_tables<T>(device, &dm);
-  if (rc || (rc = model->collision_tables<T>(device, &dc))) return rc;
-  const int nq = model->desc.nq;
-  Staging st(s);
-  const bool host = flags & IKG_FLAG_HOST_POINTERS;
-  const void* dq = q;
-  const void* dt = targets;
-  void* dout = out;
-  const int32_t* didx = (const int32_t*)st.in(idx, sizeof(int32_t) * n);
-  if (host) {
-    dq = st.in(q, sizeof(T) * nq * B);
-    dt = st.in(targets, sizeof(T) * 12 * B);
-    dout = st.out(sizeof(T) * B);
-  }
+  int rc = model->kin.get<T>(model->mu, device, &dm);
+  if (rc || (rc = model->col.get<T>(model->mu, device, &dc))) return rc;
+  Staging st(s, flags);
+  const int32_t* didx = (const int32_t*)st.upload(idx, sizeof(int32_t) * n);
+  const void* dq = st.in(q, sizeof(T) * model->desc.nq * B);
+  const void* dt = st.in(targets, sizeof(T) * 12 * B);
+  void* dout = st.out(out, sizeof(T) * B);
   if (st.rc) return st.rc;
   hipError_t e = ikg::launch_distance<T>(dm, dc, dq, dt, B, didx, n, dout, s);
   if (e != hipSuccess) return hip_fail(e, "ikg distance kernel launch");
-  if (host) st.back(out, dout, sizeof(T) * B);
-  if (st.rc) return st.rc;
-  e = hipStreamSynchronize(s);  // the staged index array is freed on return
-  if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-  return IKG_OK;
+  return st.finish(true);  // the staged index array is freed on return
 }
 
 template <typename T>
 int target_env_t(ikg_model* model, int device, const void* targets, int64_t B, const int32_t* geoms, int32_t n,
                  uint8_t* out, hipStream_t s, uint32_t flags) {
   const ikg::KCollision<T>* dc = nullptr;
-  int rc = model->collision_tables<T>(device, &dc);
+  int rc = model->col.get<T>(model->mu, device, &dc);
   if (rc) return rc;
-  Staging st(s);
-  const bool host = flags & IKG_FLAG_HOST_POINTERS;
-  const void* dt = targets;
-  uint8_t* dout = out;
-  const int32_t* dg = (const int32_t*)st.in(geoms, sizeof(int32_t) * n);
-  if (host) {
-    dt = st.in(targets, sizeof(T) * 12 * B);
-    dout = (uint8_t*)st.out(B);
-  }
+  Staging st(s, flags);
+  const int32_t* dg = (const int32_t*)st.upload(geoms, sizeof(int32_t) * n);
+  const void* dt = st.in(targets, sizeof(T) * 12 * B);
+  uint8_t* dout = (uint8_t*)st.out(out, B);
   if (st.rc) return st.rc;
   hipError_t e = ikg::launch_target_env<T>(dc, dt, B, dg, n, dout, s);
   if (e != hipSuccess) return hip_fail(e, "ikg target/env kernel launch");
-  if (host) st.back(out, dout, B);
-  if (st.rc) return st.rc;
-  e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-  return IKG_OK;
+  return st.finish(true);  // the staged geometry list is freed on return
 }
 
 extern "C" {
@@ -953,18 +903,19 @@ int ikg_distance_batch(const ikg_model* model, int device, int dtype, const void
   if (n_pairs < 1 || !pair_idx) return fail(IKG_EINVAL, "pair_idx must list at least one pair");
   if (B > 0 && (!q || !targets || !dist)) return fail(IKG_EINVAL, "q, targets and dist are required");
   if (dtype != IKG_F64 && dtype != IKG_F32) return fail(IKG_EINVAL, "dtype %d unknown", dtype);
-  if (!model->has_collision) return fail(IKG_EINVAL, "no collision scene attached (ikg_model_set_collision)");
+  if (!model->col.present) return fail(IKG_EINVAL, "%s", model->col.missing);
   for (int32_t k = 0; k < n_pairs; ++k)
-    if (pair_idx[k] < 0 || pair_idx[k] >= model->c64.n_pairs)
-      return fail(IKG_EINVAL, "pair_idx[%d] = %d outside [0, %d)", k, pair_idx[k], model->c64.n_pairs);
+    if (pair_idx[k] < 0 || pair_idx[k] >= model->col.k64.n_pairs)
+      return fail(IKG_EINVAL, "pair_idx[%d] = %d outside [0, %d)", k, pair_idx[k], model->col.k64.n_pairs);
   if (B > kMaxWaves) return fail(IKG_EINVAL, "B=%lld too large for one launch (at most %lld)", (long long)B, (long long)kMaxWaves);
   DeviceGuard g(device);
   if (g.rc) return g.rc;
   if (B == 0) return IKG_OK;
   ikg_model* m = const_cast<ikg_model*>(model);
   hipStream_t s = (hipStream_t)stream;
-  return dtype == IKG_F64 ? distance_t<double>(m, device, q, targets, B, pair_idx, n_pairs, dist, s, flags)
-                          : distance_t<float>(m, device, q, targets, B, pair_idx, n_pairs, dist, s, flags);
+  return by_dtype(dtype, [&](auto t) {
+    return distance_t<decltype(t)>(m, device, q, targets, B, pair_idx, n_pairs, dist, s, flags);
+  });
 }
 
 int ikg_target_env_batch(const ikg_model* model, int device, int dtype, const void* targets, int64_t B,
@@ -976,17 +927,18 @@ int ikg_target_env_batch(const ikg_model* model, int device, int dtype, const vo
   if (n_geoms < 1 || !geoms) return fail(IKG_EINVAL, "geoms must list at least one geometry");
   if (B > 0 && (!targets || !in_collision)) return fail(IKG_EINVAL, "targets and in_collision are required");
   if (dtype != IKG_F64 && dtype != IKG_F32) return fail(IKG_EINVAL, "dtype %d unknown", dtype);
-  if (!model->has_collision) return fail(IKG_EINVAL, "no collision scene attached (ikg_model_set_collision)");
+  if (!model->col.present) return fail(IKG_EINVAL, "%s", model->col.missing);
   for (int32_t k = 0; k < n_geoms; ++k)
-    if (geoms[k] < 0 || geoms[k] >= model->c64.n_geoms || geoms[k] == model->c64.target_geom)
+    if (geoms[k] < 0 || geoms[k] >= model->col.k64.n_geoms || geoms[k] == model->col.k64.target_geom)
       return fail(IKG_EINVAL, "geoms[%d] = %d is not a scene geometry other than the target", k, geoms[k]);
   DeviceGuard g(device);
   if (g.rc) return g.rc;
   if (B == 0) return IKG_OK;
   ikg_model* m = const_cast<ikg_model*>(model);
   hipStream_t s = (hipStream_t)stream;
-  return dtype == IKG_F64 ? target_env_t<double>(m, device, targets, B, geoms, n_geoms, in_collision, s, flags)
-                          : target_env_t<float>(m, device, targets, B, geoms, n_geoms, in_collision, s, flags);
+  return by_dtype(dtype, [&](auto t) {
+    return target_env_t<decltype(t)>(m, device, targets, B, geoms, n_geoms, in_collision, s, flags);
+  });
 }
 
 }  // extern "C"
@@ -996,37 +948,23 @@ template <typename T>
 int frame_kin_t(ikg_model* model, int device, const void* q, const void* v, const void* qd, const void* vd, int64_t B,
                 int rf, const ikg_frame_kin_out& out, hipStream_t s, uint32_t flags) {
   const ikg::KModel<T>* dm = nullptr;
-  int rc = model->device_tables<T>(device, &dm);
+  int rc = model->kin.get<T>(model->mu, device, &dm);
   if (rc) return rc;
   const int nq = model->desc.nq;
-  const size_t sz[7] = {24, 12, (size_t)12 * nq, (size_t)12 * nq, 12, 12, 12};  // per state
-  void* host_out[7] = {out.placement, out.velocity, out.J, out.dJ, out.dJv, out.err, out.derr};
-  void* dev_out[7];
-  Staging st(s);
-  const bool host = flags & IKG_FLAG_HOST_POINTERS;
-  const void *dq = q, *dv = v, *dqd = qd, *dvd = vd;
+  const size_t row = sizeof(T) * B, rows = row * nq;
+  Staging st(s, flags);
   const bool des = out.err || out.derr;
-  if (host) {
-    dq = st.in(q, sizeof(T) * nq * B);
-    dv = st.in(v, sizeof(T) * nq * B);
-    if (des) {
-      dqd = st.in(qd, sizeof(T) * nq * B);
-      dvd = st.in(vd, sizeof(T) * nq * B);
-    }
-  }
-  for (int i = 0; i < 7; ++i) dev_out[i] = host && host_out[i] ? st.out(sizeof(T) * sz[i] * B) : host_out[i];
+  const void* dq = st.in(q, rows);
+  const void* dv = st.in(v, rows);
+  const void* dqd = des ? st.in(qd, rows) : nullptr;
+  const void* dvd = des ? st.in(vd, rows) : nullptr;
+  const ikg::FrameKinOut o{st.out(out.placement, 24 * row), st.out(out.velocity, 12 * row), st.out(out.J, 12 * rows),
+                           st.out(out.dJ, 12 * rows),       st.out(out.dJv, 12 * row),      st.out(out.err, 12 * row),
+                           st.out(out.derr, 12 * row)};
   if (st.rc) return st.rc;
-  ikg::FrameKinOut o{dev_out[0], dev_out[1], dev_out[2], dev_out[3], dev_out[4], dev_out[5], dev_out[6]};
-  hipError_t e = ikg::launch_frame_kin<T>(dm, nq, model->spec, dq, dv, des ? dqd : nullptr, des ? dvd : nullptr, B, rf, o, s);
+  hipError_t e = ikg::launch_frame_kin<T>(dm, nq, model->spec, dq, dv, dqd, dvd, B, rf, o, s);
   if (e != hipSuccess) return hip_fail(e, "ikg frame kinematics kernel launch");
-  if (host) {
-    for (int i = 0; i < 7; ++i)
-      if (host_out[i]) st.back(host_out[i], dev_out[i], sizeof(T) * sz[i] * B);
-    if (st.rc) return st.rc;
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-  }
-  return IKG_OK;
+  return st.finish();
 }
 
 extern "C" {
@@ -1048,8 +986,9 @@ int ikg_frame_kinematics_batch(const ikg_model* model, int device, int dtype, co
   if (B == 0) return IKG_OK;
   ikg_model* m = const_cast<ikg_model*>(model);
   hipStream_t s = (hipStream_t)stream;
-  return dtype == IKG_F64 ? frame_kin_t<double>(m, device, q, v, q_des, v_des, B, rf, *out, s, flags)
-                          : frame_kin_t<float>(m, device, q, v, q_des, v_des, B, rf, *out, s, flags);
+  return by_dtype(dtype, [&](auto t) {
+    return frame_kin_t<decltype(t)>(m, device, q, v, q_des, v_des, B, rf, *out, s, flags);
+  });
 }
 
 }  // extern "C"
@@ -1059,34 +998,20 @@ template <typename T>
 int dynamics_t(ikg_model* model, int device, const void* q, const void* v, int64_t B, const ikg_dynamics_out& out,
                hipStream_t s, uint32_t flags) {
   const ikg::KModel<T>* dm = nullptr;
-  int rc = model->device_tables<T>(device, &dm);
+  int rc = model->kin.get<T>(model->mu, device, &dm);
   if (rc) return rc;
   const ikg::KInertia<T>* di = nullptr;
-  if ((rc = model->inertia_tables<T>(device, &di))) return rc;
+  if ((rc = model->ine.get<T>(model->mu, device, &di))) return rc;
   const int nq = model->desc.nq;
-  const size_t sz[3] = {(size_t)nq * nq, (size_t)nq, (size_t)nq};  // per state
-  void* host_out[3] = {out.M, out.nle, out.g};
-  void* dev_out[3];
-  Staging st(s);
-  const bool host = flags & IKG_FLAG_HOST_POINTERS;
-  const void *dq = q, *dv = v;
-  if (host) {
-    dq = st.in(q, sizeof(T) * nq * B);
-    dv = st.in(v, sizeof(T) * nq * B);
-  }
-  for (int i = 0; i < 3; ++i) dev_out[i] = host && host_out[i] ? st.out(sizeof(T) * sz[i] * B) : host_out[i];
+  const size_t rows = sizeof(T) * nq * B;
+  Staging st(s, flags);
+  const void* dq = st.in(q, rows);
+  const void* dv = st.in(v, rows);
+  const ikg::DynOut o{st.out(out.M, rows * nq), st.out(out.nle, rows), st.out(out.g, rows)};
   if (st.rc) return st.rc;
-  const ikg::DynOut o{dev_out[0], dev_out[1], dev_out[2]};
   hipError_t e = ikg::launch_dynamics<T>(dm, di, nq, dq, dv, B, o, s);
   if (e != hipSuccess) return hip_fail(e, "ikg dynamics kernel launch");
-  if (host) {
-    for (int i = 0; i < 3; ++i)
-      if (host_out[i]) st.back(host_out[i], dev_out[i], sizeof(T) * sz[i] * B);
-    if (st.rc) return st.rc;
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-  }
-  return IKG_OK;
+  return st.finish();
 }
 
 extern "C" {
@@ -1098,14 +1023,10 @@ int ikg_model_set_inertia(ikg_model* m, const ikg_inertia_desc* d) {
   const int bad = ikg::check_inertia_desc(*d, m->desc.nq, &why);
   if (bad >= 0) return fail(IKG_EINVAL, "inertia of body %d: %s", bad, why);
   std::lock_guard<std::mutex> lock(m->mu);
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  free_slots(m->ine64);  // re-uploaded lazily; callers must not race a launch
-  free_slots(m->ine32);
-  if (prev >= 0) (void)hipSetDevice(prev);
-  ikg::build_kinertia<double>(m->desc, *d, m->i64);
-  ikg::build_kinertia<float>(m->desc, *d, m->i32);
-  m->has_inertia = true;
+  m->ine.reset();
+  ikg::build_kinertia<double>(m->desc, *d, m->ine.k64);
+  ikg::build_kinertia<float>(m->desc, *d, m->ine.k32);
+  m->ine.present = true;
   return IKG_OK;
 }
 
@@ -1118,20 +1039,18 @@ int ikg_dynamics_batch(const ikg_model* model, int device, int dtype, const void
   if (dtype != IKG_F64 && dtype != IKG_F32) return fail(IKG_EINVAL, "dtype %d unknown", dtype);
   if (B > 0 && !q) return fail(IKG_EINVAL, "q is required");
   if (B > (int64_t)1 << 40) return fail(IKG_EINVAL, "B too large");
-  if (!model->has_inertia) return fail(IKG_EINVAL, "no body inertias attached (ikg_model_set_inertia)");
-  if (flags & IKG_FLAG_HOST_POINTERS) {  // the device code is built with -ffinite-math-only
-    const int64_t n = B * model->desc.nq;
-    int rc = dtype == IKG_F64 ? check_finite<double>(q, n, "q") : check_finite<float>(q, n, "q");
-    if (!rc && v) rc = dtype == IKG_F64 ? check_finite<double>(v, n, "v") : check_finite<float>(v, n, "v");
-    if (rc) return rc;
-  }
+  if (!model->ine.present) return fail(IKG_EINVAL, "%s", model->ine.missing);
+  const int nq = model->desc.nq;  // (the device code is built with -ffinite-math-only)
+  if (int rc = by_dtype(dtype, [&](auto t) {
+        return check_finite_rows<decltype(t)>(flags, B, {{q, nq, "q"}, {v, nq, "v"}});
+      }))
+    return rc;
   DeviceGuard g(device);
   if (g.rc) return g.rc;
   if (B == 0) return IKG_OK;
   ikg_model* m = const_cast<ikg_model*>(model);
   hipStream_t s = (hipStream_t)stream;
-  return dtype == IKG_F64 ? dynamics_t<double>(m, device, q, v, B, *out, s, flags)
-                          : dynamics_t<float>(m, device, q, v, B, *out, s, flags);
+  return by_dtype(dtype, [&](auto t) { return dynamics_t<decltype(t)>(m, device, q, v, B, *out, s, flags); });
 }
 
 }  // extern "C"
@@ -1143,75 +1062,118 @@ namespace {
 // e' per state: 3.6 KB at nq = 15) stays at 240 MB whatever the batch
 constexpr int64_t kCtlChunk = 65536;
 
+// the gains, with the rollout's two time steps `dt` (null for the torque law alone)
+int check_control_params(const ikg_control_params& c, const double* dt) {
+  const double g[8] = {c.Kp, c.Kv, c.Kf, c.Kt, c.lambda_reg, c.qp_reg, dt ? dt[0] : 0.0, dt ? dt[1] : 0.0};
+  int rc = check_finite<double>(g, dt ? 8 : 6, dt ? "gains / dt" : "gains");
+  if (!rc) rc = check_finite<double>(c.fc_bias, 12, "fc_bias");
+  if (rc) return rc;
+  if (!(c.lambda_reg > 0) || !(c.qp_reg > 0))
+    return fail(IKG_EINVAL, "lambda_reg and qp_reg must be > 0 (they make the factored matrices positive definite)");
+  return IKG_OK;
+}
+
+// What every fp64 controller entry starts with: the scratch of destroyed graphs
+// is released and the joint and inertia tables are on the device.
+struct CtlTables {
+  const ikg::KModel<double>* dm = nullptr;
+  const ikg::KInertia<double>* di = nullptr;
+};
+int controller_tables(ikg_model* model, int device, hipStream_t s, CtlTables& t) {
+  if (!ikg::stream_capturing(s)) ikg::ws_drain(&model->ws);
+  if (int rc = model->kin.get<double>(model->mu, device, &t.dm)) return rc;
+  return model->ine.get<double>(model->mu, device, &t.di);
+}
+
+// `bytes` of the model's stream-ordered scratch, poisoned, around body(ws, what):
+// freed whatever the body returns; `what` names the launch that failed.
+template <typename F>
+int with_scratch(ikg_model* model, size_t bytes, hipStream_t s, const char* name, F&& body) {
+  void* ws = nullptr;
+  hipError_t e = ikg::ws_alloc(&model->ws, &ws, bytes, s);
+  if (e != hipSuccess) return fail(IKG_ENOMEM, "%s scratch (%zu bytes): %s", name, bytes, hipGetErrorString(e));
+  ikg::poison_float(ws, bytes, s);
+  const char* what = "";
+  e = body(ws, what);
+  const hipError_t ef = ikg::ws_free(&model->ws, ws, s);
+  if (e != hipSuccess) return hip_fail(e, what);
+  if (ef != hipSuccess) return fail(IKG_EHIP, "%s scratch free: %s", name, hipGetErrorString(ef));
+  return IKG_OK;
+}
+
+// pass(off, n) over the batch in chunks, until one fails
+template <typename F>
+hipError_t for_chunks(int64_t B, int64_t chunk, F&& pass) {
+  hipError_t e = hipSuccess;
+  for (int64_t off = 0; off < B && e == hipSuccess; off += chunk) e = pass(off, std::min(chunk, B - off));
+  return e;
+}
+
+// state `off` of a [B, width] fp64 array; null (an absent array) stays null
+const void* row_at(const void* p, size_t width, int64_t off) { return p ? (const double*)p + width * off : nullptr; }
+void* row_at(void* p, size_t width, int64_t off) { return p ? (double*)p + width * off : nullptr; }
+
+// The torque law's scratch for `chunk` states: M, J, nle, dJ v, e, e'
+struct CtlScratch {
+  double *M, *J, *nle, *dJv, *err, *derr, *end;
+  static size_t per_state(int nq) { return (size_t)nq * nq + 12 * (size_t)nq + nq + 36; }
+  CtlScratch(void* ws, int nq, int64_t chunk) {
+    M = (double*)ws;
+    J = M + (size_t)nq * nq * chunk;
+    nle = J + 12 * (size_t)nq * chunk;
+    dJv = nle + (size_t)nq * chunk;
+    err = dJv + 12 * chunk;
+    derr = err + 12 * chunk;
+    end = derr + 12 * chunk;
+  }
+};
+
+// frame kinematics, then dynamics, of n states into the scratch -> the input of the solve and step kernels
+hipError_t torque_law_inputs(const ikg_model* model, const CtlTables& t, const CtlScratch& w, const void* q,
+                             const void* v, const void* qd, const void* vd, int64_t n, hipStream_t s,
+                             const char*& what, ikg::CtlIn& in) {
+  const int nq = model->desc.nq;
+  in = ikg::CtlIn{w.M, w.nle, w.J, w.dJv, w.err, w.derr};
+  what = "ikg frame kinematics kernel launch";
+  const hipError_t e =
+      ikg::launch_frame_kin<double>(t.dm, nq, model->spec, q, v, qd, vd, n, IKG_LOCAL_WORLD_ALIGNED,
+                                    ikg::FrameKinOut{nullptr, nullptr, w.J, nullptr, w.dJv, w.err, w.derr}, s);
+  if (e != hipSuccess) return e;
+  what = "ikg dynamics kernel launch";
+  return ikg::launch_dynamics<double>(t.dm, t.di, nq, q, v, n, ikg::DynOut{w.M, w.nle, nullptr}, s);
+}
+
 int control_torque(ikg_model* model, int device, const void* q, const void* v, const void* qd, const void* vd,
                    int64_t B, const ikg_control_params& params, const ikg_control_out& out, hipStream_t s,
                    uint32_t flags) {
   using T = double;
-  if (!ikg::stream_capturing(s)) ikg::ws_drain(&model->ws);  // scratch of destroyed graphs
-  const ikg::KModel<T>* dm = nullptr;
-  int rc = model->device_tables<T>(device, &dm);
-  if (rc) return rc;
-  const ikg::KInertia<T>* di = nullptr;
-  if ((rc = model->inertia_tables<T>(device, &di))) return rc;
+  CtlTables t;
+  if (int rc = controller_tables(model, device, s, t)) return rc;
   const int nq = model->desc.nq;
+  const size_t rows = sizeof(T) * nq * B;
+  Staging st(s, flags);
+  const void *dq = st.in(q, rows), *dv = st.in(v, rows), *dqd = st.in(qd, rows), *dvd = st.in(vd, rows);
   const size_t sz[5] = {(size_t)nq, (size_t)nq, 12, 72, 12};  // per state
-  void* host_out[5] = {out.tau, out.qdd, out.xdd, out.Lambda, out.fc};
-  void* dev_out[5];
-  Staging st(s);
-  const bool host = flags & IKG_FLAG_HOST_POINTERS;
-  const void *dq = q, *dv = v, *dqd = qd, *dvd = vd;
-  if (host) {
-    dq = st.in(q, sizeof(T) * nq * B);
-    dv = st.in(v, sizeof(T) * nq * B);
-    dqd = st.in(qd, sizeof(T) * nq * B);
-    dvd = st.in(vd, sizeof(T) * nq * B);
-  }
-  for (int i = 0; i < 5; ++i) dev_out[i] = host && host_out[i] ? st.out(sizeof(T) * sz[i] * B) : host_out[i];
+  void* o[5] = {out.tau, out.qdd, out.xdd, out.Lambda, out.fc};
+  for (int i = 0; i < 5; ++i) o[i] = st.out(o[i], sizeof(T) * sz[i] * B);
   if (st.rc) return st.rc;
   const int64_t chunk = std::min(B, kCtlChunk);
-  const size_t per = (size_t)nq * nq + nq + 12 * (size_t)nq + 36;
-  void* ws = nullptr;
-  hipError_t e = ikg::ws_alloc(&model->ws, &ws, sizeof(T) * per * chunk, s);
-  if (e != hipSuccess) return fail(IKG_ENOMEM, "controller scratch (%zu bytes): %s", sizeof(T) * per * chunk,
-                                   hipGetErrorString(e));
-  ikg::poison_float(ws, sizeof(T) * per * chunk, s);
-  T* wM = (T*)ws;
-  T* wJ = wM + (size_t)nq * nq * chunk;
-  T* wn = wJ + 12 * (size_t)nq * chunk;
-  T* wdJv = wn + (size_t)nq * chunk;
-  T* werr = wdJv + 12 * chunk;
-  T* wderr = werr + 12 * chunk;
   const ikg::KCtl<T> prm = ikg::make_kctl<T>(params);
-  const char* what = "";
-  for (int64_t off = 0; off < B && e == hipSuccess; off += chunk) {
-    const int64_t n = std::min(chunk, B - off);
-    auto at = [&](const void* p, size_t w) { return p ? (const void*)((const T*)p + w * off) : nullptr; };
-    auto ao = [&](void* p, size_t w) { return p ? (void*)((T*)p + w * off) : nullptr; };
-    const ikg::FrameKinOut fo{nullptr, nullptr, wJ, nullptr, wdJv, werr, wderr};
-    what = "ikg frame kinematics kernel launch";
-    e = ikg::launch_frame_kin<T>(dm, nq, model->spec, at(dq, nq), at(dv, nq), at(dqd, nq), at(dvd, nq), n,
-                                 IKG_LOCAL_WORLD_ALIGNED, fo, s);
-    if (e != hipSuccess) break;
-    what = "ikg dynamics kernel launch";
-    e = ikg::launch_dynamics<T>(dm, di, nq, at(dq, nq), at(dv, nq), n, ikg::DynOut{wM, wn, nullptr}, s);
-    if (e != hipSuccess) break;
-    what = "ikg controller solve kernel launch";
-    const ikg::CtlIn in{wM, wn, wJ, wdJv, werr, wderr};
-    const ikg::CtlOut co{ao(dev_out[0], sz[0]), ao(dev_out[1], sz[1]), ao(dev_out[2], sz[2]), ao(dev_out[3], sz[3]),
-                         ao(dev_out[4], sz[4])};
-    e = ikg::launch_control_solve(in, nq, n, prm, co, s);
-  }
-  const hipError_t ef = ikg::ws_free(&model->ws, ws, s);
-  if (e != hipSuccess) return hip_fail(e, what);
-  if (ef != hipSuccess) return hip_fail(ef, "controller scratch free");
-  if (host) {
-    for (int i = 0; i < 5; ++i)
-      if (host_out[i]) st.back(host_out[i], dev_out[i], sizeof(T) * sz[i] * B);
-    if (st.rc) return st.rc;
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-  }
-  return IKG_OK;
+  const int rc = with_scratch(
+      model, sizeof(T) * CtlScratch::per_state(nq) * chunk, s, "controller", [&](void* ws, const char*& what) {
+        const CtlScratch w(ws, nq, chunk);
+        return for_chunks(B, chunk, [&](int64_t off, int64_t n) {
+          ikg::CtlIn in;
+          const hipError_t e = torque_law_inputs(model, t, w, row_at(dq, nq, off), row_at(dv, nq, off),
+                                                 row_at(dqd, nq, off), row_at(dvd, nq, off), n, s, what, in);
+          if (e != hipSuccess) return e;
+          what = "ikg controller solve kernel launch";
+          const ikg::CtlOut co{row_at(o[0], sz[0], off), row_at(o[1], sz[1], off), row_at(o[2], sz[2], off),
+                               row_at(o[3], sz[3], off), row_at(o[4], sz[4], off)};
+          return ikg::launch_control_solve(in, nq, n, prm, co, s);
+        });
+      });
+  return rc ? rc : st.finish();
 }
 
 }  // namespace
@@ -1241,23 +1203,12 @@ int ikg_control_torque_batch(const ikg_model* model, int device, const void* q, 
   if (B < 0) return fail(IKG_EINVAL, "B must be >= 0");
   if (B > 0 && (!q || !q_des)) return fail(IKG_EINVAL, "q and q_des are required");
   if (B > (int64_t)1 << 40) return fail(IKG_EINVAL, "B too large");
-  if (!model->has_inertia) return fail(IKG_EINVAL, "no body inertias attached (ikg_model_set_inertia)");
-  {
-    const double g[6] = {params->Kp, params->Kv, params->Kf, params->Kt, params->lambda_reg, params->qp_reg};
-    int rc = check_finite<double>(g, 6, "gains");
-    if (!rc) rc = check_finite<double>(params->fc_bias, 12, "fc_bias");
-    if (rc) return rc;
-    if (!(params->lambda_reg > 0) || !(params->qp_reg > 0))
-      return fail(IKG_EINVAL, "lambda_reg and qp_reg must be > 0 (they make the factored matrices positive definite)");
-  }
-  if (flags & IKG_FLAG_HOST_POINTERS) {  // the device code is built with -ffinite-math-only
-    const int64_t n = B * model->desc.nq;
-    int rc = check_finite<double>(q, n, "q");
-    if (!rc && v) rc = check_finite<double>(v, n, "v");
-    if (!rc) rc = check_finite<double>(q_des, n, "q_des");
-    if (!rc && v_des) rc = check_finite<double>(v_des, n, "v_des");
-    if (rc) return rc;
-  }
+  if (!model->ine.present) return fail(IKG_EINVAL, "%s", model->ine.missing);
+  if (int rc = check_control_params(*params, nullptr)) return rc;
+  const int nq = model->desc.nq;  // (the device code is built with -ffinite-math-only)
+  if (int rc = check_finite_rows<double>(
+          flags, B, {{q, nq, "q"}, {v, nq, "v"}, {q_des, nq, "q_des"}, {v_des, nq, "v_des"}}))
+    return rc;
   DeviceGuard g(device);
   if (g.rc) return g.rc;
   if (B == 0) return IKG_OK;
@@ -1273,53 +1224,30 @@ namespace {
 int forward_dynamics(ikg_model* model, int device, const void* q, const void* v, const void* tau, int64_t B,
                      void* qdd, hipStream_t s, uint32_t flags) {
   using T = double;
-  if (!ikg::stream_capturing(s)) ikg::ws_drain(&model->ws);
-  const ikg::KModel<T>* dm = nullptr;
-  int rc = model->device_tables<T>(device, &dm);
-  if (rc) return rc;
-  const ikg::KInertia<T>* di = nullptr;
-  if ((rc = model->inertia_tables<T>(device, &di))) return rc;
+  CtlTables t;
+  if (int rc = controller_tables(model, device, s, t)) return rc;
   const int nq = model->desc.nq;
-  Staging st(s);
-  const bool host = flags & IKG_FLAG_HOST_POINTERS;
-  const void *dq = q, *dv = v, *dtau = tau;
-  void* dout = qdd;
-  if (host) {
-    dq = st.in(q, sizeof(T) * nq * B);
-    dv = st.in(v, sizeof(T) * nq * B);
-    dtau = st.in(tau, sizeof(T) * nq * B);
-    dout = st.out(sizeof(T) * nq * B);
-  }
+  const size_t rows = sizeof(T) * nq * B;
+  Staging st(s, flags);
+  const void *dq = st.in(q, rows), *dv = st.in(v, rows), *dtau = st.in(tau, rows);
+  void* dout = st.out(qdd, rows);
   if (st.rc) return st.rc;
   const int64_t chunk = std::min(B, kCtlChunk);
-  const size_t per = (size_t)nq;  // nle
-  void* ws = nullptr;
-  hipError_t e = ikg::ws_alloc(&model->ws, &ws, sizeof(T) * per * chunk, s);
-  if (e != hipSuccess) return fail(IKG_ENOMEM, "forward dynamics scratch (%zu bytes): %s", sizeof(T) * per * chunk,
-                                   hipGetErrorString(e));
-  ikg::poison_float(ws, sizeof(T) * per * chunk, s);
-  T* wn = (T*)ws;
-  const char* what = "";
-  for (int64_t off = 0; off < B && e == hipSuccess; off += chunk) {
-    const int64_t n = std::min(chunk, B - off);
-    auto at = [&](const void* p) { return p ? (const void*)((const T*)p + (size_t)nq * off) : nullptr; };
-    what = "ikg dynamics kernel launch";
-    e = ikg::launch_dynamics<T>(dm, di, nq, at(dq), at(dv), n, ikg::DynOut{nullptr, wn, nullptr}, s);
-    if (e != hipSuccess) break;
-    what = "ikg forward dynamics kernel launch";
-    e = ikg::launch_forward_dynamics(dm, di, nq, at(dq), wn, at(dtau), n, (T*)dout + (size_t)nq * off, s);
-  }
-  const hipError_t ef = ikg::ws_free(&model->ws, ws, s);
-  if (e != hipSuccess) return hip_fail(e, what);
-  if (ef != hipSuccess) return hip_fail(ef, "forward dynamics scratch free");
-  if (host) {
-    st.back(qdd, dout, sizeof(T) * nq * B);
-    if (st.rc) return st.rc;
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-  }
-  return IKG_OK;
+  const int rc = with_scratch(  // nle
+      model, sizeof(T) * nq * chunk, s, "forward dynamics", [&](void* wn, const char*& what) {
+        return for_chunks(B, chunk, [&](int64_t off, int64_t n) {
+          what = "ikg dynamics kernel launch";
+          const hipError_t e = ikg::launch_dynamics<T>(t.dm, t.di, nq, row_at(dq, nq, off), row_at(dv, nq, off), n,
+                                                       ikg::DynOut{nullptr, wn, nullptr}, s);
+          if (e != hipSuccess) return e;
+          what = "ikg forward dynamics kernel launch";
+          return ikg::launch_forward_dynamics(t.dm, t.di, nq, row_at(dq, nq, off), wn, row_at(dtau, nq, off), n,
+                                              row_at(dout, nq, off), s);
+        });
+      });
+  return rc ? rc : st.finish();
 }
+
 
 int check_bezier(const ikg_bezier* c, int dim, const char* what) {
   if (!c || !c->points) return fail(IKG_EINVAL, "%s: curve or its points are NULL", what);
@@ -1344,105 +1272,72 @@ int control_rollout(ikg_model* model, int device, const void* q0, const void* v0
                     const ikg_bezier& bq, const ikg_bezier& bv, const ikg_rollout_params& params,
                     const ikg_rollout_out& out, hipStream_t s, uint32_t flags) {
   using T = double;
-  if (!ikg::stream_capturing(s)) ikg::ws_drain(&model->ws);
-  const ikg::KModel<T>* dm = nullptr;
-  int rc = model->device_tables<T>(device, &dm);
-  if (rc) return rc;
-  const ikg::KInertia<T>* di = nullptr;
-  if ((rc = model->inertia_tables<T>(device, &di))) return rc;
+  CtlTables t;
+  if (int rc = controller_tables(model, device, s, t)) return rc;
   const int nq = model->desc.nq;
   const int64_t ticks = params.ticks, every = params.record_every;
   const int64_t R = every > 0 ? ticks / every : 0;
   const size_t sz[6] = {(size_t)nq, (size_t)nq, 1, (size_t)(R * nq), (size_t)(R * nq), (size_t)(R * nq)};  // per state
-  void* host_out[6] = {out.q, out.v, out.t, R ? out.q_hist : nullptr, R ? out.v_hist : nullptr,
-                       R ? out.tau_hist : nullptr};
-  void* dev_out[6];
-  Staging st(s);
-  const bool host = flags & IKG_FLAG_HOST_POINTERS;
-  const void *dq0 = q0, *dv0 = v0, *dt0 = t0;
-  if (host) {
-    dq0 = st.in(q0, sizeof(T) * nq * B);
-    dv0 = st.in(v0, sizeof(T) * nq * B);
-    dt0 = st.in(t0, sizeof(T) * B);
-  }
-  for (int i = 0; i < 6; ++i) dev_out[i] = host && host_out[i] ? st.out(sizeof(T) * sz[i] * B) : host_out[i];
+  void* o[6] = {out.q, out.v, out.t, R ? out.q_hist : nullptr, R ? out.v_hist : nullptr, R ? out.tau_hist : nullptr};
+  Staging st(s, flags);
+  const void* dq0 = st.in(q0, sizeof(T) * nq * B);
+  const void* dv0 = st.in(v0, sizeof(T) * nq * B);
+  const void* dt0 = st.in(t0, sizeof(T) * B);
+  for (int i = 0; i < 6; ++i) o[i] = st.out(o[i], sizeof(T) * sz[i] * B);
   if (st.rc) return st.rc;
   std::vector<double> tab;
   append_curve(tab, bq, nq);
   append_curve(tab, bv, nq);
-  // scratch: the torque law's (M, J, nle, dJ v, e, e'), the desired state, the
-  // state rows the caller did not ask for, and the curve table
+  // scratch: the torque law's, the desired state, the state rows the caller
+  // did not ask for, and the curve table
   const int64_t chunk = std::min(B, kCtlChunk);
-  const size_t per = (size_t)nq * nq + 12 * (size_t)nq + nq + 36 + 2 * (size_t)nq + (dev_out[0] ? 0 : nq) +
-                     (dev_out[1] ? 0 : nq) + (dev_out[2] ? 0 : 1);
-  const size_t bytes = sizeof(T) * (per * chunk + tab.size());
-  void* ws = nullptr;
-  hipError_t e = ikg::ws_alloc(&model->ws, &ws, bytes, s);
-  if (e != hipSuccess) return fail(IKG_ENOMEM, "rollout scratch (%zu bytes): %s", bytes, hipGetErrorString(e));
-  ikg::poison_float(ws, bytes, s);
-  T* wM = (T*)ws;
-  T* wJ = wM + (size_t)nq * nq * chunk;
-  T* wn = wJ + 12 * (size_t)nq * chunk;
-  T* wdJv = wn + (size_t)nq * chunk;
-  T* werr = wdJv + 12 * chunk;
-  T* wderr = werr + 12 * chunk;
-  T* wqd = wderr + 12 * chunk;
-  T* wvd = wqd + (size_t)nq * chunk;
-  T* next = wvd + (size_t)nq * chunk;
-  T* sq = nullptr;
-  T* sv = nullptr;
-  T* stt = nullptr;
-  if (!dev_out[0]) sq = next, next += (size_t)nq * chunk;
-  if (!dev_out[1]) sv = next, next += (size_t)nq * chunk;
-  if (!dev_out[2]) stt = next, next += chunk;
-  T* wtab = next;
+  const size_t per = CtlScratch::per_state(nq) + 2 * (size_t)nq + (o[0] ? 0 : nq) + (o[1] ? 0 : nq) + (o[2] ? 0 : 1);
   const ikg::KCtl<T> prm = ikg::make_kctl<T>(params.control);
-  const char* what = "rollout curve table upload";
-  e = ikg::launch_table_write(wtab, tab.data(), tab.size(), s);
-  for (int64_t off = 0; off < B && e == hipSuccess; off += chunk) {
-    const int64_t n = std::min(chunk, B - off);
-    auto at = [&](const void* p, size_t w) { return p ? (const void*)((const T*)p + w * off) : nullptr; };
-    auto ao = [&](void* p, size_t w) { return p ? (void*)((T*)p + w * off) : nullptr; };
-    ikg::StepArgs a;
-    a.q = dev_out[0] ? ao(dev_out[0], sz[0]) : sq;
-    a.v = dev_out[1] ? ao(dev_out[1], sz[1]) : sv;
-    a.t = dev_out[2] ? ao(dev_out[2], sz[2]) : stt;
-    a.qdes = wqd;
-    a.vdes = wvd;
-    a.cv = ikg::RolloutCurves{wtab, bq.n_points, bv.n_points, bq.t_min, bq.t_max, bq.mult, bv.t_min, bv.t_max, bv.mult};
-    a.dt_sim = params.dt_sim;
-    a.dt_traj = params.dt_traj;
-    a.q_hist = ao(dev_out[3], sz[3]);
-    a.v_hist = ao(dev_out[4], sz[4]);
-    a.tau_hist = ao(dev_out[5], sz[5]);
-    a.R = R;
-    a.slot = -1;
-    what = "ikg rollout init kernel launch";
-    e = ikg::launch_rollout_init(at(dq0, nq), at(dv0, nq), at(dt0, 1), nq, n, a, s);
-    for (int64_t k = 0; k < ticks && e == hipSuccess; ++k) {
-      const ikg::FrameKinOut fo{nullptr, nullptr, wJ, nullptr, wdJv, werr, wderr};
-      what = "ikg frame kinematics kernel launch";
-      e = ikg::launch_frame_kin<T>(dm, nq, model->spec, a.q, a.v, wqd, wvd, n, IKG_LOCAL_WORLD_ALIGNED, fo, s);
-      if (e != hipSuccess) break;
-      what = "ikg dynamics kernel launch";
-      e = ikg::launch_dynamics<T>(dm, di, nq, a.q, a.v, n, ikg::DynOut{wM, wn, nullptr}, s);
-      if (e != hipSuccess) break;
-      what = "ikg control step kernel launch";
-      a.slot = (R && (k + 1) % every == 0 && (k + 1) / every <= R) ? (k + 1) / every - 1 : -1;
-      e = ikg::launch_control_step(ikg::CtlIn{wM, wn, wJ, wdJv, werr, wderr}, nq, n, prm, a, s);
-    }
-  }
-  const hipError_t ef = ikg::ws_free(&model->ws, ws, s);
-  if (e != hipSuccess) return hip_fail(e, what);
-  if (ef != hipSuccess) return hip_fail(ef, "rollout scratch free");
-  if (host) {
-    for (int i = 0; i < 6; ++i)
-      if (host_out[i]) st.back(host_out[i], dev_out[i], sizeof(T) * sz[i] * B);
-    if (st.rc) return st.rc;
-    e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-  }
-  return IKG_OK;
+  const int rc = with_scratch(
+      model, sizeof(T) * (per * chunk + tab.size()), s, "rollout", [&](void* ws, const char*& what) {
+        const CtlScratch w(ws, nq, chunk);
+        T* wqd = w.end;
+        T* wvd = wqd + (size_t)nq * chunk;
+        T* next = wvd + (size_t)nq * chunk;
+        T *sq = nullptr, *sv = nullptr, *stt = nullptr;
+        if (!o[0]) sq = next, next += (size_t)nq * chunk;
+        if (!o[1]) sv = next, next += (size_t)nq * chunk;
+        if (!o[2]) stt = next, next += chunk;
+        T* wtab = next;
+        what = "rollout curve table upload";
+        const hipError_t e = ikg::launch_table_write(wtab, tab.data(), tab.size(), s);
+        if (e != hipSuccess) return e;
+        return for_chunks(B, chunk, [&](int64_t off, int64_t n) {
+          ikg::StepArgs a;
+          a.q = o[0] ? row_at(o[0], sz[0], off) : sq;
+          a.v = o[1] ? row_at(o[1], sz[1], off) : sv;
+          a.t = o[2] ? row_at(o[2], sz[2], off) : stt;
+          a.qdes = wqd;
+          a.vdes = wvd;
+          a.cv = ikg::RolloutCurves{wtab,     bq.n_points, bv.n_points, bq.t_min, bq.t_max,
+                                    bq.mult,  bv.t_min,    bv.t_max,    bv.mult};
+          a.dt_sim = params.dt_sim;
+          a.dt_traj = params.dt_traj;
+          a.q_hist = row_at(o[3], sz[3], off);
+          a.v_hist = row_at(o[4], sz[4], off);
+          a.tau_hist = row_at(o[5], sz[5], off);
+          a.R = R;
+          a.slot = -1;
+          what = "ikg rollout init kernel launch";
+          hipError_t e = ikg::launch_rollout_init(row_at(dq0, nq, off), row_at(dv0, nq, off), row_at(dt0, 1, off), nq,
+                                                  n, a, s);
+          for (int64_t k = 0; k < ticks && e == hipSuccess; ++k) {
+            ikg::CtlIn in;
+            e = torque_law_inputs(model, t, w, a.q, a.v, wqd, wvd, n, s, what, in);
+            if (e != hipSuccess) break;
+            what = "ikg control step kernel launch";
+            a.slot = (R && (k + 1) % every == 0 && (k + 1) / every <= R) ? (k + 1) / every - 1 : -1;
+            e = ikg::launch_control_step(in, nq, n, prm, a, s);
+          }
+          return e;
+        });
+      });
+  return rc ? rc : st.finish();
 }
 
 }  // namespace
@@ -1456,14 +1351,9 @@ int ikg_forward_dynamics_batch(const ikg_model* model, int device, const void* q
   if (B < 0) return fail(IKG_EINVAL, "B must be >= 0");
   if (B > 0 && (!q || !tau || !qdd)) return fail(IKG_EINVAL, "q, tau and qdd are required");
   if (B > (int64_t)1 << 40) return fail(IKG_EINVAL, "B too large");
-  if (!model->has_inertia) return fail(IKG_EINVAL, "no body inertias attached (ikg_model_set_inertia)");
-  if (flags & IKG_FLAG_HOST_POINTERS) {  // the device code is built with -ffinite-math-only
-    const int64_t n = B * model->desc.nq;
-    int rc = check_finite<double>(q, n, "q");
-    if (!rc && v) rc = check_finite<double>(v, n, "v");
-    if (!rc) rc = check_finite<double>(tau, n, "tau");
-    if (rc) return rc;
-  }
+  if (!model->ine.present) return fail(IKG_EINVAL, "%s", model->ine.missing);
+  const int nq = model->desc.nq;  // (the device code is built with -ffinite-math-only)
+  if (int rc = check_finite_rows<double>(flags, B, {{q, nq, "q"}, {v, nq, "v"}, {tau, nq, "tau"}})) return rc;
   DeviceGuard g(device);
   if (g.rc) return g.rc;
   if (B == 0) return IKG_OK;
@@ -1480,8 +1370,7 @@ int ikg_bezier_eval_batch(int device, const double* points, int32_t n_points, in
   if (K < 0) return fail(IKG_EINVAL, "K must be >= 0");
   if (K > 0 && (!times || !out)) return fail(IKG_EINVAL, "times and out are required");
   if (K > (int64_t)1 << 40) return fail(IKG_EINVAL, "K too large");
-  const bool host = flags & IKG_FLAG_HOST_POINTERS;
-  if (host) {
+  if (flags & IKG_FLAG_HOST_POINTERS) {
     const double* t = (const double*)times;
     for (int64_t k = 0; k < K; ++k)
       if (!(t[k] >= t_min && t[k] <= t_max))
@@ -1493,20 +1382,16 @@ int ikg_bezier_eval_batch(int device, const double* points, int32_t n_points, in
   hipStream_t s = (hipStream_t)stream;
   std::vector<double> tab;
   append_curve(tab, c, dim);
-  Staging st(s);
-  double* dtab = (double*)st.in_alloc(sizeof(double) * tab.size());
-  const void* dt = host ? st.in(times, sizeof(double) * K) : times;
-  void* dout = host ? st.out(sizeof(double) * K * dim) : out;
+  Staging st(s, flags);
+  double* dtab = (double*)st.alloc(sizeof(double) * tab.size());
+  const void* dt = st.in(times, sizeof(double) * K);
+  void* dout = st.out(out, sizeof(double) * K * dim);
   if (st.rc) return st.rc;
   hipError_t e = ikg::launch_table_write(dtab, tab.data(), tab.size(), s);
   if (e == hipSuccess)
     e = ikg::launch_bezier_eval(dtab, n_points, dim, t_min, t_max, mult, (const double*)dt, K, (double*)dout, s);
   if (e != hipSuccess) return hip_fail(e, "ikg bezier kernel launch");
-  if (host) st.back(out, dout, sizeof(double) * K * dim);
-  if (st.rc) return st.rc;
-  e = hipStreamSynchronize(s);  // the table is freed on return
-  if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-  return IKG_OK;
+  return st.finish(true);  // the table is freed on return
 }
 
 void ikg_rollout_params_default(ikg_rollout_params* p) {
@@ -1528,31 +1413,18 @@ int ikg_control_rollout(const ikg_model* model, int device, const void* q0, cons
   if (B < 0) return fail(IKG_EINVAL, "B must be >= 0");
   if (B > 0 && !q0) return fail(IKG_EINVAL, "q0 is required");
   if (B > (int64_t)1 << 40) return fail(IKG_EINVAL, "B too large");
-  if (!model->has_inertia) return fail(IKG_EINVAL, "no body inertias attached (ikg_model_set_inertia)");
+  if (!model->ine.present) return fail(IKG_EINVAL, "%s", model->ine.missing);
   const int nq = model->desc.nq;
   int rc = check_bezier(q_curve, nq, "q_curve");
   if (!rc) rc = check_bezier(v_curve, nq, "v_curve");
   if (rc) return rc;
-  {
-    const ikg_control_params& c = params->control;
-    const double g[8] = {c.Kp, c.Kv, c.Kf, c.Kt, c.lambda_reg, c.qp_reg, params->dt_sim, params->dt_traj};
-    rc = check_finite<double>(g, 8, "gains / dt");
-    if (!rc) rc = check_finite<double>(c.fc_bias, 12, "fc_bias");
-    if (rc) return rc;
-    if (!(c.lambda_reg > 0) || !(c.qp_reg > 0))
-      return fail(IKG_EINVAL, "lambda_reg and qp_reg must be > 0 (they make the factored matrices positive definite)");
-    if (params->ticks < 0 || params->record_every < 0)
-      return fail(IKG_EINVAL, "ticks and record_every must be >= 0");
-    if ((out->q_hist || out->v_hist || out->tau_hist) && params->record_every == 0)
-      return fail(IKG_EINVAL, "a history output needs record_every > 0");
-  }
-  if (flags & IKG_FLAG_HOST_POINTERS) {  // the device code is built with -ffinite-math-only
-    const int64_t n = B * nq;
-    rc = check_finite<double>(q0, n, "q0");
-    if (!rc && v0) rc = check_finite<double>(v0, n, "v0");
-    if (!rc && t0) rc = check_finite<double>(t0, B, "t0");
-    if (rc) return rc;
-  }
+  const double dt[2] = {params->dt_sim, params->dt_traj};
+  if ((rc = check_control_params(params->control, dt))) return rc;
+  if (params->ticks < 0 || params->record_every < 0) return fail(IKG_EINVAL, "ticks and record_every must be >= 0");
+  if ((out->q_hist || out->v_hist || out->tau_hist) && params->record_every == 0)
+    return fail(IKG_EINVAL, "a history output needs record_every > 0");
+  // (the device code is built with -ffinite-math-only)
+  if ((rc = check_finite_rows<double>(flags, B, {{q0, nq, "q0"}, {v0, nq, "v0"}, {t0, 1, "t0"}}))) return rc;
   DeviceGuard g(device);
   if (g.rc) return g.rc;
   if (B == 0) return IKG_OK;
@@ -1570,7 +1442,7 @@ namespace {
 int jit_code_locked(ikg_model* m, int dtype) {
   std::vector<char>& code = m->jit_code[dtype == IKG_F64 ? 0 : 1];
   if (!code.empty()) return IKG_OK;
-  const std::string src = dtype == IKG_F64 ? ikg::jit_source(m->k64) : ikg::jit_source(m->k32);
+  const std::string src = dtype == IKG_F64 ? ikg::jit_source(m->kin.k64) : ikg::jit_source(m->kin.k32);
   const std::string err = ikg::jit_compile(src, code);
   if (!err.empty()) {
     code.clear();

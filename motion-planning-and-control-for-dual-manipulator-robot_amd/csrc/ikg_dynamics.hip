@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "ikg_dynamics.hpp"
 #include "ikg_launch.hpp"
@@ -60,6 +61,53 @@ __device__ inline void tile_store(const T* __restrict__ tile, T* __restrict__ ds
   } else {
     for (int i = lane; i < n; i += 64) dst[i] = tile[i];
   }
+}
+
+// The phase executor of ikg_dynamics.hpp in a kernel: lane r runs row r, a
+// barrier ends the phase (a workgroup is one wave).  The lane's row of Lambda
+// stays in its registers.
+template <typename T>
+struct LaneRows {
+  int r;
+  T lam_[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
+  template <typename F>
+  __device__ void operator()(F&& fn) {
+    fn(r);
+    __syncthreads();
+  }
+  __device__ T* lam(int) { return lam_; }
+};
+
+// state p of the scratch -> its workspace, spread over the state's G lanes (no barrier)
+template <typename T>
+__device__ inline void ctl_ws_load_lanes(const CtlWs<T>& w, const CtlIn& in, int64_t p, int r, int G) {
+  const int nq = w.nq;
+  const T* gM = (const T*)in.M + p * nq * nq;
+  const T* gJ = (const T*)in.J + p * 12 * nq;
+  for (int i = r; i < nq * nq; i += G) w.M[(i / nq) * w.ld + i % nq] = gM[i];
+  for (int i = r; i < 12 * nq; i += G) w.J[(i / nq) * w.ld + i % nq] = gJ[i];
+  if (r < nq) {
+    w.Md[r] = gM[r * nq + r];
+    w.nle[r] = ((const T*)in.nle)[p * nq + r];
+  }
+  if (r < 12) {
+    w.dJv[r] = ((const T*)in.dJv)[p * 12 + r];
+    w.e[r] = ((const T*)in.err)[p * 12 + r];
+    w.ed[r] = ((const T*)in.derr)[p * 12 + r];
+  }
+}
+
+// The geometry of every kernel here: G lanes per state (16 for nq <= 16, else
+// 32), one wave per workgroup.  launch(g, nblocks) starts the kernel
+// specialised for G = g.value and returns its status.
+template <typename F>
+hipError_t launch_per_state(int nq, int64_t B, F&& launch) {
+  if (B <= 0) return hipSuccess;
+  const int states = nq <= 16 ? 4 : 2;
+  const int64_t nblocks = (B + states - 1) / states;
+  if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
+  return nq <= 16 ? launch(std::integral_constant<int, 16>{}, (unsigned)nblocks)
+                  : launch(std::integral_constant<int, 32>{}, (unsigned)nblocks);
 }
 
 }  // namespace
@@ -106,6 +154,9 @@ __global__ __launch_bounds__(64) void ikg_dynamics_kernel(const KModel<T>* __res
   cw_sincos(live ? q[p * nq + b] : T(0), &s, &c);
   const T qd = (live && v) ? v[p * nq + b] : T(0);
 
+  // (the forward pass is written out here and in the forward-dynamics kernel: as
+  // one shared function it moved fp64 M, nle, g in the last bit with the joint
+  // loads inside, and cost this kernel 1.7 % with only the rounds inside)
   DynBody<T> uni, me;
   dyn_universe(grav, ref, uni);
   me = uni;
@@ -182,23 +233,17 @@ __global__ __launch_bounds__(64) void ikg_dynamics_kernel(const KModel<T>* __res
   }
 }
 
-template <typename T, int G>
-static hipError_t launch_dynamics_g(const KModel<T>* dm, const KInertia<T>* di, int nq, const T* q, const T* v,
-                                    int64_t B, const DynOut& o, hipStream_t s) {
-  constexpr int kStates = 64 / G;
-  const int64_t nblocks = (B + kStates - 1) / kStates;
-  if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
-  const size_t lds = o.M ? sizeof(T) * kStates * nq * nq : 0;
-  hipLaunchKernelGGL((ikg_dynamics_kernel<T, G>), dim3((unsigned)nblocks), dim3(64), lds, s, dm, di, q, v, B, o);
-  return hipGetLastError();
-}
-
 template <typename T>
 hipError_t launch_dynamics(const KModel<T>* dm, const KInertia<T>* di, int nq, const void* q, const void* v,
                            int64_t B, const DynOut& o, hipStream_t s) {
-  if (B <= 0 || !(o.M || o.nle || o.g)) return hipSuccess;
-  if (nq <= 16) return launch_dynamics_g<T, 16>(dm, di, nq, (const T*)q, (const T*)v, B, o, s);
-  return launch_dynamics_g<T, 32>(dm, di, nq, (const T*)q, (const T*)v, B, o, s);
+  if (!(o.M || o.nle || o.g)) return hipSuccess;
+  return launch_per_state(nq, B, [&](auto g, unsigned nblocks) {
+    constexpr int G = decltype(g)::value;
+    const size_t lds = o.M ? sizeof(T) * (64 / G) * nq * nq : 0;
+    hipLaunchKernelGGL((ikg_dynamics_kernel<T, G>), dim3(nblocks), dim3(64), lds, s, dm, di, (const T*)q,
+                       (const T*)v, B, o);
+    return hipGetLastError();
+  });
 }
 
 // ---------------------------------------------------------------- controller solve
@@ -218,58 +263,11 @@ __global__ __launch_bounds__(64) void ikg_control_solve_kernel(CtlIn in, int nq,
   const int64_t p = live ? p0 + grp : B - 1;
   CtlWs<T> w;
   ctl_ws_bind(reinterpret_cast<T*>(smem) + (size_t)grp * ctl_ws_len(nq), nq, w);
-  const T* gM = (const T*)in.M + p * nq * nq;
-  const T* gJ = (const T*)in.J + p * 12 * nq;
-  for (int i = r; i < nq * nq; i += G) w.M[(i / nq) * w.ld + i % nq] = gM[i];
-  for (int i = r; i < 12 * nq; i += G) w.J[(i / nq) * w.ld + i % nq] = gJ[i];
-  if (r < nq) {
-    w.Md[r] = gM[r * nq + r];
-    w.nle[r] = ((const T*)in.nle)[p * nq + r];
-  }
-  if (r < 12) {
-    w.dJv[r] = ((const T*)in.dJv)[p * 12 + r];
-    w.e[r] = ((const T*)in.err)[p * 12 + r];
-    w.ed[r] = ((const T*)in.derr)[p * 12 + r];
-  }
+  ctl_ws_load_lanes(w, in, p, r, G);
   __syncthreads();
-#pragma unroll 1
-  for (int k = 0; k < nq; ++k) {
-    ldl_step(w.M, w.ld, nq, k, r);
-    __syncthreads();
-  }
-  ctl_pivots(w, r);
-  __syncthreads();
-  ctl_forward(w, prm, r);
-  __syncthreads();
-  ctl_opspace(w, prm, r);
-  __syncthreads();
-#pragma unroll 1
-  for (int k = 0; k < 6; ++k) {
-    ctl_opspace_step(w, k, r);
-    __syncthreads();
-  }
-  T lam[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
-  ctl_lambda(w, prm, r, lam);
-  __syncthreads();
-  ctl_normal(w, prm, r);
-  __syncthreads();
-#pragma unroll 1
-  for (int k = 0; k < nq; ++k) {
-    ldl_step(w.H, w.ld, nq, k, r);
-    __syncthreads();
-  }
-  ctl_check(w, r);
-  __syncthreads();
-#pragma unroll 1
-  for (int k = 0; k < nq; ++k) {
-    ctl_solve_fwd(w, k, r);
-    __syncthreads();
-  }
-#pragma unroll 1
-  for (int k = nq - 1; k >= 0; --k) {
-    ctl_solve_bwd(w, k, r);
-    __syncthreads();
-  }
+  LaneRows<T> rows{r};
+  control_solve_phases(w, prm, rows);
+  const T(&lam)[6] = rows.lam_;
   if (!live) return;
   if (r < nq) {
     const T t = ctl_tau(w, prm, r);
@@ -288,16 +286,12 @@ __global__ __launch_bounds__(64) void ikg_control_solve_kernel(CtlIn in, int nq,
 
 hipError_t launch_control_solve(const CtlIn& in, int nq, int64_t B, const KCtl<double>& prm, const CtlOut& o,
                                 hipStream_t s) {
-  if (B <= 0) return hipSuccess;
-  const int G = nq <= 16 ? 16 : 32;
-  const int64_t nblocks = (B + 64 / G - 1) / (64 / G);
-  if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
-  const size_t lds = sizeof(double) * (64 / G) * ctl_ws_len(nq);
-  if (G == 16)
-    hipLaunchKernelGGL((ikg_control_solve_kernel<16>), dim3((unsigned)nblocks), dim3(64), lds, s, in, nq, B, prm, o);
-  else
-    hipLaunchKernelGGL((ikg_control_solve_kernel<32>), dim3((unsigned)nblocks), dim3(64), lds, s, in, nq, B, prm, o);
-  return hipGetLastError();
+  return launch_per_state(nq, B, [&](auto g, unsigned nblocks) {
+    constexpr int G = decltype(g)::value;
+    const size_t lds = sizeof(double) * (64 / G) * ctl_ws_len(nq);
+    hipLaunchKernelGGL((ikg_control_solve_kernel<G>), dim3(nblocks), dim3(64), lds, s, in, nq, B, prm, o);
+    return hipGetLastError();
+  });
 }
 
 // ---------------------------------------------------------------- forward dynamics
@@ -391,38 +385,21 @@ __global__ __launch_bounds__(64) void ikg_forward_dynamics_kernel(const KModel<d
     }
   }
   __syncthreads();
-#pragma unroll 1
-  for (int k = 0; k < nq; ++k) {
-    ldl_step(f.M, f.ld, nq, k, b);
-    __syncthreads();
-  }
-#pragma unroll 1
-  for (int k = 0; k < nq; ++k) {
-    ctl_solve_fwd(f, k, b);
-    __syncthreads();
-  }
-#pragma unroll 1
-  for (int k = nq - 1; k >= 0; --k) {
-    ctl_solve_bwd(f, k, b);
-    __syncthreads();
-  }
+  LaneRows<T> rows{b};
+  ldl_factor(f.M, f.ld, nq, rows);
+  ctl_substitute(f, rows);
   if (live && body) qdd[p * nq + b] = f.qdd[b];
 }
 
 hipError_t launch_forward_dynamics(const KModel<double>* dm, const KInertia<double>* di, int nq, const void* q,
                                    const void* nle, const void* tau, int64_t B, void* qdd, hipStream_t s) {
-  if (B <= 0) return hipSuccess;
-  const int G = nq <= 16 ? 16 : 32;
-  const int64_t nblocks = (B + 64 / G - 1) / (64 / G);
-  if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
-  const size_t lds = sizeof(double) * (64 / G) * fd_ws_len(nq);
-  if (G == 16)
-    hipLaunchKernelGGL((ikg_forward_dynamics_kernel<16>), dim3((unsigned)nblocks), dim3(64), lds, s, dm, di,
-                       (const double*)q, (const double*)nle, (const double*)tau, B, (double*)qdd);
-  else
-    hipLaunchKernelGGL((ikg_forward_dynamics_kernel<32>), dim3((unsigned)nblocks), dim3(64), lds, s, dm, di,
-                       (const double*)q, (const double*)nle, (const double*)tau, B, (double*)qdd);
-  return hipGetLastError();
+  return launch_per_state(nq, B, [&](auto g, unsigned nblocks) {
+    constexpr int G = decltype(g)::value;
+    const size_t lds = sizeof(double) * (64 / G) * fd_ws_len(nq);
+    hipLaunchKernelGGL((ikg_forward_dynamics_kernel<G>), dim3(nblocks), dim3(64), lds, s, dm, di, (const double*)q,
+                       (const double*)nle, (const double*)tau, B, (double*)qdd);
+    return hipGetLastError();
+  });
 }
 
 // ---------------------------------------------------------------- Bezier curves
@@ -536,75 +513,18 @@ __global__ __launch_bounds__(64) void ikg_control_step_kernel(CtlIn in, int nq, 
   T* tab = base + (size_t)(64 / G) * step_ws_len(nq);
   const int ntab = (nq + 1) * (a.cv.nq_pts + a.cv.nv_pts);
   for (int i = lane; i < ntab; i += 64) tab[i] = a.cv.table[i];
-  const T* gM = (const T*)in.M + p * nq * nq;
-  const T* gJ = (const T*)in.J + p * 12 * nq;
-  for (int i = r; i < nq * nq; i += G) w.M[(i / nq) * w.ld + i % nq] = gM[i];
-  for (int i = r; i < 12 * nq; i += G) w.J[(i / nq) * w.ld + i % nq] = gJ[i];
-  if (r < nq) {
-    w.Md[r] = gM[r * nq + r];
-    w.nle[r] = ((const T*)in.nle)[p * nq + r];
-  }
-  if (r < 12) {
-    w.dJv[r] = ((const T*)in.dJv)[p * 12 + r];
-    w.e[r] = ((const T*)in.err)[p * 12 + r];
-    w.ed[r] = ((const T*)in.derr)[p * 12 + r];
-  }
+  ctl_ws_load_lanes(w, in, p, r, G);
   const bool row = live && r < nq;
   T q = row ? ((const T*)a.q)[p * nq + r] : T(0);
   T v = row ? ((const T*)a.v)[p * nq + r] : T(0);
   const T t = ((const T*)a.t)[p] + a.dt_traj;
   __syncthreads();
-#pragma unroll 1
-  for (int k = 0; k < nq; ++k) {
-    ldl_step(w.M, w.ld, nq, k, r);
-    __syncthreads();
-  }
-  ctl_pivots(w, r);
-  __syncthreads();
-  ctl_forward(w, prm, r);
-  __syncthreads();
-  ctl_opspace(w, prm, r);
-  __syncthreads();
-#pragma unroll 1
-  for (int k = 0; k < 6; ++k) {
-    ctl_opspace_step(w, k, r);
-    __syncthreads();
-  }
-  T lam[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
-  ctl_lambda(w, prm, r, lam);
-  __syncthreads();
-  ctl_normal(w, prm, r);
-  __syncthreads();
-#pragma unroll 1
-  for (int k = 0; k < nq; ++k) {
-    ldl_step(w.H, w.ld, nq, k, r);
-    __syncthreads();
-  }
-  ctl_check(w, r);
-  __syncthreads();
-#pragma unroll 1
-  for (int k = 0; k < nq; ++k) {
-    ctl_solve_fwd(w, k, r);
-    __syncthreads();
-  }
-#pragma unroll 1
-  for (int k = nq - 1; k >= 0; --k) {
-    ctl_solve_bwd(w, k, r);
-    __syncthreads();
-  }
+  LaneRows<T> rows{r};
+  control_solve_phases(w, prm, rows);
   const T tau = step_rhs(w, prm, flag, r);
   __syncthreads();
   fd_view(w, flag, f);
-#pragma unroll 1
-  for (int k = 0; k < nq; ++k) {
-    ctl_solve_fwd(f, k, r);
-    __syncthreads();
-  }
-#pragma unroll 1
-  for (int k = nq - 1; k >= 0; --k) {
-    ctl_solve_bwd(f, k, r);
-    __syncthreads();
-  }
+  ctl_substitute(f, rows);
   if (!live) return;
   if (r < nq) {
     step_integrate(a.dt_sim, f.qdd[r], q, v);
@@ -625,22 +545,18 @@ __global__ __launch_bounds__(64) void ikg_control_step_kernel(CtlIn in, int nq, 
 
 hipError_t launch_control_step(const CtlIn& in, int nq, int64_t B, const KCtl<double>& prm, const StepArgs& a,
                                hipStream_t s) {
-  if (B <= 0) return hipSuccess;
-  const int G = nq <= 16 ? 16 : 32;
-  const int64_t nblocks = (B + 64 / G - 1) / (64 / G);
-  if (nblocks > 0x7fffffff) return hipErrorInvalidValue;
-  const size_t lds =
-      sizeof(double) * ((64 / G) * step_ws_len(nq) + rollout_table_len(nq, a.cv.nq_pts, a.cv.nv_pts));
-  if (lds > 65536) {  // long curves on a wide model: above the default limit of dynamic LDS
-    const void* fn = G == 16 ? (const void*)ikg_control_step_kernel<16> : (const void*)ikg_control_step_kernel<32>;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  if (G == 16)
-    hipLaunchKernelGGL((ikg_control_step_kernel<16>), dim3((unsigned)nblocks), dim3(64), lds, s, in, nq, B, prm, a);
-  else
-    hipLaunchKernelGGL((ikg_control_step_kernel<32>), dim3((unsigned)nblocks), dim3(64), lds, s, in, nq, B, prm, a);
-  return hipGetLastError();
+  return launch_per_state(nq, B, [&](auto g, unsigned nblocks) {
+    constexpr int G = decltype(g)::value;
+    const size_t lds =
+        sizeof(double) * ((64 / G) * step_ws_len(nq) + rollout_table_len(nq, a.cv.nq_pts, a.cv.nv_pts));
+    if (lds > 65536) {  // long curves on a wide model: above the default limit of dynamic LDS
+      const hipError_t e = hipFuncSetAttribute((const void*)ikg_control_step_kernel<G>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((ikg_control_step_kernel<G>), dim3(nblocks), dim3(64), lds, s, in, nq, B, prm, a);
+    return hipGetLastError();
+  });
 }
 
 template hipError_t launch_dynamics<double>(const KModel<double>*, const KInertia<double>*, int, const void*,

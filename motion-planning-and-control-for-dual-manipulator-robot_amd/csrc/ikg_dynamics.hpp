@@ -300,6 +300,20 @@ IKG_HD inline void dyn_inertia_add(DynInertia<T>& A, const DynInertia<T>& B) {
   for (int i = 0; i < 6; ++i) A.I[i] += B.I[i];
 }
 
+// The forward pass of one state on the host, parents before children: the
+// universe, every body's state and motion subspace (v null: zero velocity)
+template <typename T>
+inline void forward_bodies(const KModel<T>& m, const KInertia<T>& in, const T* q, const T* v, DynBody<T>& uni,
+                           DynBody<T>* body, T (*S)[6]) {
+  dyn_universe(in.grav, in.ref, uni);
+  for (int i = 0; i < m.nq; ++i) {
+    T s, c;
+    cw_sincos(q[i], &s, &c);
+    const DynBody<T>& par = m.jparent[i] >= 0 ? body[m.jparent[i]] : uni;
+    dyn_forward(par, m.jR[i], m.jt[i], m.jaxis[i], s, c, v ? v[i] : T(0), body[i], S[i]);
+  }
+}
+
 // One state on the host, body by body in the order the kernel's lane group
 // works (ikg_dynamics.hip): forward pass, subtree sums over j ascending, then
 // the rows of M.  M [nq,nq], nle [nq], g [nq]; any may be null.
@@ -310,12 +324,8 @@ inline void dynamics_state(const KModel<T>& m, const KInertia<T>& in, const T* q
   DynInertia<T> W[kMaxNq];
   T S[kMaxNq][6], f[kMaxNq][6], f0[kMaxNq][6];
   DynBody<T> uni;
-  dyn_universe(in.grav, in.ref, uni);
+  forward_bodies(m, in, q, v, uni, body, S);
   for (int i = 0; i < nq; ++i) {
-    T s, c;
-    cw_sincos(q[i], &s, &c);
-    const DynBody<T>& par = m.jparent[i] >= 0 ? body[m.jparent[i]] : uni;
-    dyn_forward(par, m.jR[i], m.jt[i], m.jaxis[i], s, c, v ? v[i] : T(0), body[i], S[i]);
     dyn_inertia_world(in.mass[i], in.h[i], in.Io[i], body[i].R, body[i].o, W[i]);
     dyn_force(W[i], body[i].v, body[i].a, f[i]);
     const T zero[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
@@ -386,13 +396,7 @@ inline void inertia_matrix_local_state(const KModel<T>& m, const KInertia<T>& in
   DynBody<T> body[kMaxNq];
   T S[kMaxNq][6];
   DynBody<T> uni;
-  dyn_universe(in.grav, in.ref, uni);
-  for (int i = 0; i < nq; ++i) {
-    T s, c;
-    cw_sincos(q[i], &s, &c);
-    const DynBody<T>& par = m.jparent[i] >= 0 ? body[m.jparent[i]] : uni;
-    dyn_forward(par, m.jR[i], m.jt[i], m.jaxis[i], s, c, T(0), body[i], S[i]);
-  }
+  forward_bodies(m, in, q, (const T*)nullptr, uni, body, S);
   for (int i = 0; i < nq * nq; ++i) M[i] = T(0);
   for (int i = 0; i < nq; ++i) {
     DynInertia<T> Ic;
@@ -624,33 +628,53 @@ IKG_HD inline T ctl_tau(const CtlWs<T>& w, const KCtl<T>& p, int r) {
   return ((p.zero_tau_mask >> r) & 1u) ? T(0) : acc;
 }
 
-// the solve's phases for one state on the host, in the kernel's order (the
-// workspace is loaded); Lambda [2,36] may be null
+// The phases in order, written once over an executor `rows`: rows(fn) runs
+// fn(r) for the rows the caller owns and then makes their writes visible to all
+// rows.  The kernel's executor is one lane per row and a barrier
+// (ikg_dynamics.hip LaneRows); the host's is a loop over r (HostRows below).
+// rows.lam(r) is where row r < 12 keeps its row of Lambda.
 template <typename T>
-inline void control_solve_phases(const CtlWs<T>& w, const KCtl<T>& p, T* Lambda) {
-  const int nq = w.nq;
-  const int R = nq > 12 ? nq : 12;
-  for (int k = 0; k < nq; ++k)
-    for (int r = 0; r < R; ++r) ldl_step(w.M, w.ld, nq, k, r);
-  for (int r = 0; r < R; ++r) ctl_pivots(w, r);
-  for (int r = 0; r < R; ++r) ctl_forward(w, p, r);
-  for (int r = 0; r < R; ++r) ctl_opspace(w, p, r);
-  for (int k = 0; k < 6; ++k)
-    for (int r = 0; r < R; ++r) ctl_opspace_step(w, k, r);
-  for (int r = 0; r < 12; ++r) {
-    T lam[6];
-    ctl_lambda(w, p, r, lam);
-    if (Lambda)
-      for (int b = 0; b < 6; ++b) Lambda[6 * r + b] = lam[b];
+struct HostRows {
+  int R;      // rows of a phase
+  T* Lambda;  // [2,36] or null
+  T spare[6];
+  template <typename F>
+  void operator()(F&& fn) {
+    for (int r = 0; r < R; ++r) fn(r);
   }
-  for (int r = 0; r < R; ++r) ctl_normal(w, p, r);
-  for (int k = 0; k < nq; ++k)
-    for (int r = 0; r < R; ++r) ldl_step(w.H, w.ld, nq, k, r);
-  for (int r = 0; r < R; ++r) ctl_check(w, r);
-  for (int k = 0; k < nq; ++k)
-    for (int r = 0; r < R; ++r) ctl_solve_fwd(w, k, r);
-  for (int k = nq - 1; k >= 0; --k)
-    for (int r = 0; r < R; ++r) ctl_solve_bwd(w, k, r);
+  T* lam(int r) { return Lambda && r < 12 ? Lambda + 6 * r : spare; }
+};
+
+// the in-place L D L^T of the n x n matrix A, a phase per column
+template <typename T, typename Rows>
+IKG_HD inline void ldl_factor(T* A, int ld, int n, Rows& rows) {
+#pragma unroll 1
+  for (int k = 0; k < n; ++k) rows([&](int r) { ldl_step(A, ld, n, k, r); });
+}
+
+// forward then backward substitution on the factor in f.H: f.rhs -> f.qdd
+template <typename T, typename Rows>
+IKG_HD inline void ctl_substitute(const CtlWs<T>& f, Rows& rows) {
+#pragma unroll 1
+  for (int k = 0; k < f.nq; ++k) rows([&](int r) { ctl_solve_fwd(f, k, r); });
+#pragma unroll 1
+  for (int k = f.nq - 1; k >= 0; --k) rows([&](int r) { ctl_solve_bwd(f, k, r); });
+}
+
+// the solve of one state whose workspace is loaded, up to w.qdd
+template <typename T, typename Rows>
+IKG_HD inline void control_solve_phases(const CtlWs<T>& w, const KCtl<T>& p, Rows& rows) {
+  ldl_factor(w.M, w.ld, w.nq, rows);
+  rows([&](int r) { ctl_pivots(w, r); });
+  rows([&](int r) { ctl_forward(w, p, r); });
+  rows([&](int r) { ctl_opspace(w, p, r); });
+#pragma unroll 1
+  for (int k = 0; k < 6; ++k) rows([&](int r) { ctl_opspace_step(w, k, r); });
+  rows([&](int r) { ctl_lambda(w, p, r, rows.lam(r)); });
+  rows([&](int r) { ctl_normal(w, p, r); });
+  ldl_factor(w.H, w.ld, w.nq, rows);
+  rows([&](int r) { ctl_check(w, r); });
+  ctl_substitute(w, rows);
 }
 
 template <typename T>
@@ -679,7 +703,8 @@ inline void control_state(int nq, const KCtl<T>& p, const T* M, const T* nle, co
   CtlWs<T> w;
   ctl_ws_bind(buf, nq, w);
   control_ws_load(w, M, nle, J, dJv, e, ed);
-  control_solve_phases(w, p, Lambda);
+  HostRows<T> rows{nq > 12 ? nq : 12, Lambda};
+  control_solve_phases(w, p, rows);
   for (int r = 0; r < nq; ++r) {
     const T t = ctl_tau(w, p, r);
     if (tau) tau[r] = t;
@@ -793,15 +818,6 @@ IKG_HD inline void fd_ws_bind(T* base, int nq, CtlWs<T>& f) {
   f.Md = f.Mr = f.Ms = f.J = f.Z = f.A = f.nle = f.e = f.ed = f.dJv = f.fc = f.xdd = nullptr;
 }
 
-template <typename T>
-inline void fd_substitute(const CtlWs<T>& f) {
-  const int nq = f.nq;
-  for (int k = 0; k < nq; ++k)
-    for (int r = 0; r < nq; ++r) ctl_solve_fwd(f, k, r);
-  for (int k = nq - 1; k >= 0; --k)
-    for (int r = 0; r < nq; ++r) ctl_solve_bwd(f, k, r);
-}
-
 // One state on the host: qdd = M^-1 (tau - nle), the forward-dynamics kernel's order
 template <typename T>
 inline void forward_dynamics_state(int nq, const T* M, const T* nle, const T* tau, T* qdd) {
@@ -813,9 +829,9 @@ inline void forward_dynamics_state(int nq, const T* M, const T* nle, const T* ta
     f.rhs[r] = tau[r] - nle[r];
   }
   *f.fail = T(0);
-  for (int k = 0; k < nq; ++k)
-    for (int r = 0; r < nq; ++r) ldl_step(f.M, f.ld, nq, k, r);
-  fd_substitute(f);
+  HostRows<T> rows{nq, nullptr};
+  ldl_factor(f.M, f.ld, nq, rows);
+  ctl_substitute(f, rows);
   for (int r = 0; r < nq; ++r) qdd[r] = f.qdd[r];
 }
 
@@ -830,10 +846,11 @@ inline void control_step_state(int nq, const KCtl<T>& p, const T* M, const T* nl
   ctl_ws_bind(buf, nq, w);
   T* flag = buf + ctl_ws_len(nq);
   control_ws_load(w, M, nle, J, dJv, e, ed);
-  control_solve_phases(w, p, (T*)nullptr);
+  HostRows<T> rows{nq > 12 ? nq : 12, nullptr};
+  control_solve_phases(w, p, rows);
   for (int r = 0; r < nq; ++r) tau[r] = step_rhs(w, p, flag, r);
   fd_view(w, flag, f);
-  fd_substitute(f);
+  ctl_substitute(f, rows);
   for (int r = 0; r < nq; ++r) step_integrate(dt, f.qdd[r], q[r], v[r]);
 }
 

@@ -445,31 +445,42 @@ extern "C" int ikg_emu_math(int fn, int64_t n, const double* x, const double* y,
   return 0;
 }
 
+// What every dynamics entry below starts with: the inertias pass
+// ikg_model_set_inertia's checks (else null) and the joint and inertia tables
+// are built into this thread's storage.
+template <typename T>
+struct EmuTables {
+  ikg::KModel<T> m;
+  ikg::KInertia<T> in;
+};
+template <typename T>
+const EmuTables<T>* emu_tables(const ikg_model_desc* d, const ikg_inertia_desc* id) {
+  const char* why = "";
+  if (ikg::check_inertia_desc(*id, d->nq, &why) >= 0) return nullptr;
+  static thread_local EmuTables<T> t;
+  ikg::build_kmodel<T>(*d, t.m);
+  ikg::build_kinertia<T>(*d, *id, t.in);
+  return &t;
+}
+
 // ikg_dynamics_batch on the CPU: the per-body functions of ikg_dynamics.hpp in
 // the kernel's order (tests/test_dynamics.py).  v and every output may be NULL.
 template <typename T>
-void emu_dyn(const ikg_model_desc* d, const ikg_inertia_desc* id, const void* q, const void* v, int64_t B, void* M,
-             void* nle, void* g) {
-  static thread_local ikg::KModel<T> m;
-  static thread_local ikg::KInertia<T> in;
-  ikg::build_kmodel<T>(*d, m);
-  ikg::build_kinertia<T>(*d, *id, in);
+int emu_dyn(const ikg_model_desc* d, const ikg_inertia_desc* id, const void* q, const void* v, int64_t B, void* M,
+            void* nle, void* g) {
+  const EmuTables<T>* t = emu_tables<T>(d, id);
+  if (!t) return -1;
   const int nq = d->nq;
   for (int64_t i = 0; i < B; ++i)
-    ikg::dynamics_state<T>(m, in, (const T*)q + nq * i, v ? (const T*)v + nq * i : nullptr,
+    ikg::dynamics_state<T>(t->m, t->in, (const T*)q + nq * i, v ? (const T*)v + nq * i : nullptr,
                            M ? (T*)M + (int64_t)nq * nq * i : nullptr, nle ? (T*)nle + nq * i : nullptr,
                            g ? (T*)g + nq * i : nullptr);
+  return 0;
 }
 
 extern "C" int ikg_emu_dynamics(const ikg_model_desc* d, const ikg_inertia_desc* id, int dtype, const void* q,
                                 const void* v, int64_t B, void* M, void* nle, void* g) {
-  const char* why = "";
-  if (ikg::check_inertia_desc(*id, d->nq, &why) >= 0) return -1;
-  if (dtype == IKG_F64)
-    emu_dyn<double>(d, id, q, v, B, M, nle, g);
-  else
-    emu_dyn<float>(d, id, q, v, B, M, nle, g);
-  return 0;
+  return dtype == IKG_F64 ? emu_dyn<double>(d, id, q, v, B, M, nle, g) : emu_dyn<float>(d, id, q, v, B, M, nle, g);
 }
 
 // The solve of ikg_control_torque_batch on the CPU (fp64): M and nle from
@@ -480,17 +491,13 @@ extern "C" int ikg_emu_control_torque(const ikg_model_desc* d, const ikg_inertia
                                       const double* v, const double* J, const double* dJv, const double* err,
                                       const double* derr, int64_t B, const ikg_control_params* p, double* tau,
                                       double* qdd, double* xdd, double* Lambda, double* fc) {
-  const char* why = "";
-  if (ikg::check_inertia_desc(*id, d->nq, &why) >= 0) return -1;
-  static thread_local ikg::KModel<double> m;
-  static thread_local ikg::KInertia<double> in;
-  ikg::build_kmodel<double>(*d, m);
-  ikg::build_kinertia<double>(*d, *id, in);
+  const EmuTables<double>* t = emu_tables<double>(d, id);
+  if (!t) return -1;
   const ikg::KCtl<double> prm = ikg::make_kctl<double>(*p);
   const int nq = d->nq;
   for (int64_t i = 0; i < B; ++i) {
     double M[ikg::kMaxNq * ikg::kMaxNq], nle[ikg::kMaxNq];
-    ikg::dynamics_state<double>(m, in, q + nq * i, v ? v + nq * i : nullptr, M, nle, nullptr);
+    ikg::dynamics_state<double>(t->m, t->in, q + nq * i, v ? v + nq * i : nullptr, M, nle, nullptr);
     ikg::control_state<double>(nq, prm, M, nle, J + 12 * nq * i, dJv + 12 * i, err + 12 * i, derr + 12 * i,
                                tau ? tau + nq * i : nullptr, qdd ? qdd + nq * i : nullptr,
                                xdd ? xdd + 12 * i : nullptr, Lambda ? Lambda + 72 * i : nullptr,
@@ -624,17 +631,13 @@ extern "C" int ikg_emu_frame_terms(const ikg_model_desc* d, const double* q, con
 // joint's own origin (inertia_matrix_local_state), then the forward-dynamics kernel's phases
 extern "C" int ikg_emu_forward_dynamics(const ikg_model_desc* d, const ikg_inertia_desc* id, const double* q,
                                         const double* v, const double* tau, int64_t B, double* qdd) {
-  const char* why = "";
-  if (ikg::check_inertia_desc(*id, d->nq, &why) >= 0) return -1;
-  static thread_local ikg::KModel<double> m;
-  static thread_local ikg::KInertia<double> in;
-  ikg::build_kmodel<double>(*d, m);
-  ikg::build_kinertia<double>(*d, *id, in);
+  const EmuTables<double>* t = emu_tables<double>(d, id);
+  if (!t) return -1;
   const int nq = d->nq;
   for (int64_t i = 0; i < B; ++i) {
     double M[ikg::kMaxNq * ikg::kMaxNq], nle[ikg::kMaxNq];
-    ikg::dynamics_state<double>(m, in, q + nq * i, v ? v + nq * i : nullptr, nullptr, nle, nullptr);
-    ikg::inertia_matrix_local_state<double>(m, in, q + nq * i, M);
+    ikg::dynamics_state<double>(t->m, t->in, q + nq * i, v ? v + nq * i : nullptr, nullptr, nle, nullptr);
+    ikg::inertia_matrix_local_state<double>(t->m, t->in, q + nq * i, M);
     ikg::forward_dynamics_state<double>(nq, M, nle, tau + nq * i, qdd + nq * i);
   }
   return 0;
@@ -661,14 +664,10 @@ extern "C" int ikg_emu_control_rollout(const ikg_model_desc* d, const ikg_inerti
                                        const double* v0, const double* t0, int64_t B, const ikg_bezier* bq,
                                        const ikg_bezier* bv, const ikg_rollout_params* p,
                                        const ikg_rollout_out* out) {
-  const char* why = "";
-  if (ikg::check_inertia_desc(*id, d->nq, &why) >= 0) return -1;
+  const EmuTables<double>* tb = emu_tables<double>(d, id);
+  if (!tb) return -1;
   if (!emu_curve_ok(bq) || !emu_curve_ok(bv) || p->ticks < 0 || p->record_every < 0) return -1;
   if ((out->q_hist || out->v_hist || out->tau_hist) && p->record_every == 0) return -1;
-  static thread_local ikg::KModel<double> m;
-  static thread_local ikg::KInertia<double> in;
-  ikg::build_kmodel<double>(*d, m);
-  ikg::build_kinertia<double>(*d, *id, in);
   const ikg::KCtl<double> prm = ikg::make_kctl<double>(p->control);
   const int nq = d->nq;
   double bcq[ikg::kMaxBezier], bcv[ikg::kMaxBezier];
@@ -691,8 +690,8 @@ extern "C" int ikg_emu_control_rollout(const ikg_model_desc* d, const ikg_inerti
       }
       if (k == p->ticks) break;
       double M[ikg::kMaxNq * ikg::kMaxNq], nle[ikg::kMaxNq], J[12 * ikg::kMaxNq], dJv[12], e[12], ed[12];
-      emu_frame_terms<double>(m, q, v, qd, vd, J, dJv, e, ed);
-      ikg::dynamics_state<double>(m, in, q, v, M, nle, nullptr);
+      emu_frame_terms<double>(tb->m, q, v, qd, vd, J, dJv, e, ed);
+      ikg::dynamics_state<double>(tb->m, tb->in, q, v, M, nle, nullptr);
       ikg::control_step_state<double>(nq, prm, M, nle, J, dJv, e, ed, p->dt_sim, q, v, tau);
       t += p->dt_traj;
       if (R && (k + 1) % every == 0) {

@@ -114,6 +114,7 @@ def test_first_torque_is_control_torques(solver, d, nextage_rollouts):
         equal = equal and np.array_equal(got, tau)
     print(f"tau_hist[:, 0] vs control_torques: {worst:.3e} of max|tau| (bound {d['tol_tau'][0]:.3e}); bit-equal: {equal}")
     assert worst <= d["tol_tau"][0]
+    assert equal  # the solve kernel and the step kernel run the same phases on the same scratch
 
 
 # ---------------------------------------------------------------- one call against another, bit for bit
