@@ -280,10 +280,7 @@ int check_variant(const ikg_model* model, const ikg_params* params) {
 // passing iterate).  Its round-2 graph-replay mismatch was the graph memory
 // node the records came from (ws_alloc, ikg_launch.hpp).  Up
 // to rec_budget() bytes of records per solve.
-static bool rec_in_batch() {
-  const char* e = getenv("IKG_TRAJ_REC");
-  return !(e && atoi(e) == 0);
-}
+static bool rec_in_batch() { return ikg::env_flag("IKG_TRAJ_REC", true); }
 // Memory of a collision solve (round 6, window checkpoints, ikg_solve.hpp):
 //  * checkpoints, one area per problem of a launch (ck_per_problem: 34 slots,
 //    17 KB in fp64, 8.7 KB in fp32 at max_iters 1,000: C2 71 MB, C3 570 MB,
@@ -300,14 +297,11 @@ static bool rec_in_batch() {
 // under a 24 GiB budget; the model's pool keeps 1.25 GiB between solves
 // (ikg_launch.hpp ws_keep_bytes).
 constexpr size_t kRecBudgetMB = 1024, kCkBudgetMB = 16384;
-static size_t rec_budget() {
-  if (const char* e = getenv("IKG_REC_BUDGET_MB")) return std::max<size_t>(1, (size_t)atoll(e)) << 20;
-  return kRecBudgetMB << 20;
+static size_t budget_bytes(const char* name, size_t mb) {
+  return std::max<size_t>(1, (size_t)ikg::env_int(name, (long long)mb)) << 20;
 }
-static size_t ck_budget() {
-  if (const char* e = getenv("IKG_CK_BUDGET_MB")) return std::max<size_t>(1, (size_t)atoll(e)) << 20;
-  return kCkBudgetMB << 20;
-}
+static size_t rec_budget() { return budget_bytes("IKG_REC_BUDGET_MB", kRecBudgetMB); }
+static size_t ck_budget() { return budget_bytes("IKG_CK_BUDGET_MB", kCkBudgetMB); }
 
 // the final record (record layout) fits a checkpoint slot (ikg_solve.hpp kCkSlot)
 static bool rec_fits(int nq) {
@@ -337,31 +331,29 @@ static int64_t rec_chunk(const ikg_params& params, int64_t units, int64_t per_un
   return (units + n - 1) / n;
 }
 
+// Whether a collision solve is offered records, but for the layout (QUAD
+// takes none), which each caller tests its own way: the collision term, the
+// compiled Nextage loop (no damping, no model-specialised kernel), records on
+// and a final record that fits a checkpoint slot.
+static bool records_apply(const ikg_model* model, const ikg_params* params, bool collision, bool jit, int nq) {
+  return collision && model->spec == ikg::kSpecNextage && !(params->lambda > 0) && !jit && rec_in_batch() &&
+         rec_fits(nq);
+}
+
 // Checkpoints and records of the collision continuation for `n` problems (one
-// chunk, see solve_batch_t): checkpoints for all n, records for the records
-// budget's capacity (a.rec_slots).  Null when the allocation fails (the
-// continuation then runs without them).
+// chunk, see solve_batch_t), in `ws`: checkpoints for all n, records for the
+// records budget's capacity (rec_slots).  All null when the allocation fails
+// (the continuation then runs without them).
 template <typename T>
-void* offer_records(ikg_model* model, ikg::BatchArgs& a, const ikg_params& params, int64_t n, int nq, hipStream_t s,
-                    bool* rec_used) {
-  const int64_t slots = std::min<int64_t>(n, std::max<int64_t>(1, (int64_t)(rec_budget() / rec_records_bytes<T>(params, nq))));
-  const size_t b_rec = (rec_records_bytes<T>(params, nq) * (size_t)slots + 255) & ~(size_t)255;
-  const size_t b_ck = (rec_ck_bytes<T>(params) * (size_t)n + 255) & ~(size_t)255;
-  const size_t b_n = (sizeof(int32_t) * (size_t)n + 255) & ~(size_t)255;
-  void* rec = nullptr;
-  if (ikg::ws_alloc(&model->ws, &rec, b_rec + b_ck + b_n, s) != hipSuccess) {
+ikg::RecBufs offer_records(ikg::Workspace& ws, const ikg_params& params, int64_t n, int nq, bool* rec_used) {
+  const size_t per = rec_records_bytes<T>(params, nq);
+  const int64_t slots = std::min<int64_t>(n, std::max<int64_t>(1, (int64_t)(rec_budget() / per)));
+  const ikg::RecLayout l(n, slots, per, rec_ck_bytes<T>(params));
+  if (ws.alloc(l) != hipSuccess) {
     (void)hipGetLastError();
-    return nullptr;
+    return {};
   }
-  a.rec = rec;
-  a.ck = (char*)rec + b_rec;
-  a.rec_n = (int32_t*)((char*)rec + b_rec + b_ck);
-  a.rec_slots = slots;
-  ikg::ws_trace("alloc rec", rec, b_rec + b_ck + b_n, s);
-  ikg::poison_float(rec, b_rec + b_ck, s);
-  ikg::poison_int(a.rec_n, sizeof(int32_t) * (size_t)n, s);
-  a.rec_used = rec_used;
-  return rec;
+  return {ws.at<void>(l.rec), ws.at<int32_t>(l.rec_n), ws.at<void>(l.ck), rec_used, slots};
 }
 
 // chunk [off, off + n) of a batch's arguments (device pointers)
@@ -422,13 +414,13 @@ int solve_batch_t(ikg_model* model, int device, const void* targets, const void*
   // (ikg_collision.hip), whatever the q0 layout; the records
   // take (max_iters + 1) x rec_len values per problem, offered up to the budget
   bool rec_used = false;
-  void* rec = nullptr;
+  ikg::Workspace rec(&model->ws, s, "rec");
   int64_t chunk = B;
   const ikg::KParams<T> kp = kparams<T>(params);
-  if (dc && model->spec == ikg::kSpecNextage && !(params->lambda > 0) && !a.jit && rec_in_batch() &&
-      rec_fits(nq) && ikg::resolve_variant<T>(kp, model->spec, a.variant, B, true) != IKG_VARIANT_QUAD) {
+  if (records_apply(model, params, dc != nullptr, a.jit != nullptr, nq) &&
+      ikg::resolve_variant<T>(kp, model->spec, a.variant, B, true) != IKG_VARIANT_QUAD) {
     chunk = rec_chunk<T>(*params, B, 1);
-    rec = offer_records<T>(model, a, *params, chunk, nq, s, &rec_used);
+    a.recs = offer_records<T>(rec, *params, chunk, nq, &rec_used);
     if (!rec) chunk = B;
     // every chunk runs the layout the whole batch would
     if (chunk < B) a.variant = ikg::resolve_variant<T>(kp, model->spec, a.variant, B, true);
@@ -437,20 +429,10 @@ int solve_batch_t(ikg_model* model, int device, const void* targets, const void*
   for (int64_t off = 0; off < B && e == hipSuccess; off += chunk) {
     const ikg::BatchArgs c = chunk < B ? batch_slice<T>(a, off, std::min(chunk, B - off), nq) : a;
     e = ikg::launch_pair_batch<T>(dm, kp, c, model->spec, s);
-    if (e != hipSuccess) {
-      if (rec) {
-        ikg::ws_trace("free rec", rec, 0, s);
-        (void)ikg::ws_free(&model->ws, rec, s);
-      }
-      return hip_fail(e, "ikg pair kernel launch");
-    }
+    if (e != hipSuccess) return hip_fail(e, "ikg pair kernel launch");
     if (dc) e = ikg::launch_collide_continue<T>(dm, dc, kp, c, model->spec, nq, model->col.k64.n_geoms, s);
   }
-  if (rec) {
-    ikg::ws_trace("free rec", rec, 0, s);
-    const hipError_t ef = ikg::ws_free(&model->ws, rec, s);
-    if (e == hipSuccess) e = ef;
-  }
+  e = rec.finish(e);
   if (e != hipSuccess) return hip_fail(e, "ikg collision continuation launch");
   return st.finish();
 }
@@ -495,41 +477,26 @@ int solve_multi_t(ikg_model* model, int device, const void* targets, int64_t T_,
   }
   // per-seed workspace, stream-ordered (capturable) allocation
   const int64_t n = T_ * S;
-  const size_t b_q = sizeof(T) * nq * n, b_err = sizeof(T) * 2 * n, b_it = sizeof(int32_t) * n;
-  char* ws = nullptr;
-  hipError_t e = ikg::ws_alloc(&model->ws, (void**)&ws, b_q + b_err + b_it + n + 64, s);
+  const ikg::MultiLayout l(n, sizeof(T), nq);
+  ikg::Workspace ws(&model->ws, s, "multistart");
+  hipError_t e = ws.alloc(l);
   if (e != hipSuccess) return fail(IKG_ENOMEM, "multistart workspace allocation: %s", hipGetErrorString(e));
-  ikg::ws_trace("alloc multistart", ws, b_q + b_err + b_it + n + 64, s);
-  ikg::poison_float(ws, b_q + b_err, s);
-  ikg::poison_int(ws + b_q + b_err, b_it + n, s);
-  a.ws_q = ws;
-  a.ws_err = ws + b_q;
-  a.ws_iters = (int32_t*)(ws + b_q + b_err);
-  a.ws_conv = (uint8_t*)(ws + b_q + b_err + b_it);
+  a.ws_q = ws.at<void>(l.q);
+  a.ws_err = ws.at<void>(l.err);
+  a.ws_iters = ws.at<int32_t>(l.iters);
+  a.ws_conv = ws.at<uint8_t>(l.conv);
   // the collision continuation's records, as solve_batch_t (same values for a
   // seed whatever call solves it)
   bool rec_used = false;
-  void* rec = nullptr;
-  if (a.collision && model->spec == ikg::kSpecNextage && !(params->lambda > 0) && !a.jit && rec_in_batch() &&
-      rec_fits(nq) && params->variant != IKG_VARIANT_QUAD) {
-    ikg::BatchArgs tmp{};
+  ikg::Workspace rec(&model->ws, s, "rec");
+  if (records_apply(model, params, a.collision != nullptr, a.jit != nullptr, nq) &&
+      params->variant != IKG_VARIANT_QUAD) {
     a.rec_chunk = rec_chunk<T>(*params, T_, S);  // targets per launch (each with its S seeds)
-    rec = offer_records<T>(model, tmp, *params, a.rec_chunk * S, nq, s, &rec_used);
-    a.rec = tmp.rec;
-    a.rec_n = tmp.rec_n;
-    a.ck = tmp.ck;
-    a.rec_slots = tmp.rec_slots;
-    a.rec_used = tmp.rec_used;
+    a.recs = offer_records<T>(rec, *params, a.rec_chunk * S, nq, &rec_used);
     if (!rec) a.rec_chunk = 0;
   }
-  e = ikg::launch_multistart<T>(dm, kparams<T>(params), a, model->spec, s);
-  if (rec) {
-    ikg::ws_trace("free rec", rec, 0, s);
-    const hipError_t ef = ikg::ws_free(&model->ws, rec, s);
-    if (e == hipSuccess) e = ef;
-  }
-  ikg::ws_trace("free multistart", ws, 0, s);
-  hipError_t e2 = ikg::ws_free(&model->ws, ws, s);
+  e = rec.finish(ikg::launch_multistart<T>(dm, kparams<T>(params), a, model->spec, s));
+  const hipError_t e2 = ws.release();
   if (e != hipSuccess) return hip_fail(e, "ikg multistart kernel launch");
   if (e2 != hipSuccess) return hip_fail(e2, "multistart workspace free");
   return st.finish();
@@ -1089,13 +1056,14 @@ int controller_tables(ikg_model* model, int device, hipStream_t s, CtlTables& t)
 // freed whatever the body returns; `what` names the launch that failed.
 template <typename F>
 int with_scratch(ikg_model* model, size_t bytes, hipStream_t s, const char* name, F&& body) {
-  void* ws = nullptr;
-  hipError_t e = ikg::ws_alloc(&model->ws, &ws, bytes, s);
+  ikg::WsLayout l;
+  l.add(bytes, ikg::WsLayout::kFloat, 1);
+  ikg::Workspace ws(&model->ws, s, name);
+  hipError_t e = ws.alloc(l);
   if (e != hipSuccess) return fail(IKG_ENOMEM, "%s scratch (%zu bytes): %s", name, bytes, hipGetErrorString(e));
-  ikg::poison_float(ws, bytes, s);
   const char* what = "";
-  e = body(ws, what);
-  const hipError_t ef = ikg::ws_free(&model->ws, ws, s);
+  e = body(ws.at<void>(0), what);
+  const hipError_t ef = ws.release();
   if (e != hipSuccess) return hip_fail(e, what);
   if (ef != hipSuccess) return fail(IKG_EHIP, "%s scratch free: %s", name, hipGetErrorString(ef));
   return IKG_OK;

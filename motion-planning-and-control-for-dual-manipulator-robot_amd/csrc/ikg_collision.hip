@@ -12,6 +12,7 @@
 //    ~745-pair check.
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstddef>
 #include <cstdlib>
 
@@ -1429,50 +1430,32 @@ constexpr int kScanSplitMax = 8;
 constexpr int32_t kScanNone = 0x7f7f7f7f;  // best[p] before any wave found an answer (a byte-fill value)
 
 // IKG_SCAN_CERT=0: the records scan without inscribed-ball certificates (A/B
-// knob, read at every launch so one process can compare both: the answers do
-// not depend on it, tests/test_gpu_collision.py)
-static int scan_cert() {
-  const char* e = getenv("IKG_SCAN_CERT");
-  return e ? atoi(e) : 1;
-}
+// knob: the answers do not depend on it, tests/test_gpu_collision.py)
+static int scan_cert() { return (int)env_int("IKG_SCAN_CERT", 1); }
 // waves of the records scan (grid-stride over the listed problems): one per
 // problem up to 65,536.  The listed count is known only on the device, so the
 // grid is sized by B and waves past it return at once.  A grid of 1,024 (one
 // wave per SIMD, ~8.5 windows each at C3) took C3 + collision 2.21 ms against
-// 1.98 (profiles/r05/collision/scan_waves/); IKG_SCAN_WAVES (read at every
-// launch) sets it for A/Bs
-// IKG_BOX_COVER=0 (read at every launch): round -2 proves no window by its box,
-// so every problem that collides at its first passing iterate has all its
-// records regenerated and scanned -- the round-5 records' work, for the tests
-// that pin the window form's answers to it (and for A/Bs)
+// 1.98 (profiles/r05/collision/scan_waves/); IKG_SCAN_WAVES sets it for A/Bs
+// IKG_BOX_COVER=0: round -2 proves no window by its box, so every problem that
+// collides at its first passing iterate has all its records regenerated and
+// scanned -- the round-5 records' work, for the tests that pin the window
+// form's answers to it (and for A/Bs)
 // The first check of a records solve: the lean pre-screen kernel checks every
 // converged problem and lists the colliding ones itself, then
 // ikg_first_check_kernel runs the window boxes over that list.  The fused form
-// (IKG_PRESCAN=1, read at every launch: one wave per problem of the batch for
-// both) carries the certificate code's registers into every problem's check --
+// (IKG_PRESCAN=1: one wave per problem of the batch for both) carries the
+// certificate code's registers into every problem's check --
 // 1 wave per SIMD in fp64, 1.6 ms for C4's 131,072-problem share; with the
 // kernels' own appends (no compaction launches) the split form is also the
 // faster at C2 (70 against 75 us) and C3 (254 against 267 us),
 // profiles/r06/records/prescan/
-static bool first_fused(int64_t B) {
-  (void)B;
-  const char* e = getenv("IKG_PRESCAN");
-  return e ? atoi(e) != 0 : false;
-}
-static int box_cover() {
-  const char* e = getenv("IKG_BOX_COVER");
-  return e ? atoi(e) != 0 : 1;
-}
-// IKG_SCAN_SPLIT (read at every launch): the split scan's wave target (0: one
-// wave per listed problem)
-static int scan_split() {
-  const char* e = getenv("IKG_SCAN_SPLIT");
-  return e ? std::max(0, atoi(e)) : 2048;
-}
+static bool first_fused() { return env_flag("IKG_PRESCAN", false); }
+static int box_cover() { return env_flag("IKG_BOX_COVER", true); }
+// IKG_SCAN_SPLIT: the split scan's wave target (0: one wave per listed problem)
+static int scan_split() { return std::max(0, (int)env_int("IKG_SCAN_SPLIT", 2048)); }
 static int64_t scan_waves(int64_t B) {
-  const char* e = getenv("IKG_SCAN_WAVES");
-  const int64_t w = e ? std::max(1, atoi(e)) : 65536;
-  return std::min<int64_t>(w, B);
+  return std::min<int64_t>(std::max(1, (int)env_int("IKG_SCAN_WAVES", 65536)), B);
 }
 // the record layout (kRec*, rec_len, store_block8) is in ikg_solve.hpp
 
@@ -2240,11 +2223,7 @@ hipError_t launch_collision(const KModel<T>* dm, const KCollision<T>* dc, const 
 
 // problems per continuation wave (IKG_CONT_G=1 selects one per wave; timing knob)
 static int cont_groups() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("IKG_CONT_G");
-    v = (e && atoi(e) == 1) ? 1 : 4;
-  }
+  static const int v = env_int("IKG_CONT_G", 4) == 1 ? 1 : 4;
   return v;
 }
 
@@ -2269,22 +2248,13 @@ struct ContWs {
 // (tools/probe/rounds.sh, kernel ms per solve, 0/1/2 rounds): C2 fp64
 // B=4096: 2.39/3.35/3.19; C3 fp32 B=65536: 5.10/5.38/5.71.  Before the
 // compaction (problems in place, ~0.5 per wave): C2 2.47/3.45/3.17, C3
-// 6.06/5.20/5.72.  IKG_HANDOFF_ROUNDS overrides (read per launch: the tests
-// run both paths).
-static int handoff_rounds() {
-  const char* e = getenv("IKG_HANDOFF_ROUNDS");
-  return e ? std::min(64, std::max(0, atoi(e))) : 0;
-}
+// 6.06/5.20/5.72.  IKG_HANDOFF_ROUNDS overrides (the tests run both paths).
+static int handoff_rounds() { return std::min(64, std::max(0, (int)env_int("IKG_HANDOFF_ROUNDS", 0))); }
 
 // least problems per stretch wave (IKG_STRETCH_PPW; timing knob)
 static int stretch_ppw() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("IKG_STRETCH_PPW");
-    v = e ? std::min(32, std::max(-1, atoi(e))) : 32;
-    if (v == 0) v = 1;
-  }
-  return v;
+  static const int v = std::min(32, std::max(-1, (int)env_int("IKG_STRETCH_PPW", 32)));
+  return v == 0 ? 1 : v;
 }
 
 template <typename T, bool DAMPED, class SP, int G>
@@ -2317,22 +2287,15 @@ static void launch_continue_t(const KModel<T>* dm, const KCollision<T>* dc, cons
     launch_continue_g<T, DAMPED, SP, 4>(dm, dc, prm, a, nq, ng, w, s);
 }
 
-// IKG_CONT_TRAJ=0 selects the interleaved continuation (read per launch: the
-// tests run both).  Above kTrajMaxB problems per launch the record windows
-// shrink below 32 iterates (kTrajBudget), so the interleaved one runs there.
+// IKG_CONT_TRAJ=0 selects the interleaved continuation (the tests run both).
+// Above kTrajMaxB problems per launch the record windows shrink below 32
+// iterates (kTrajBudget), so the interleaved one runs there.
 constexpr int64_t kTrajMaxB = 262144;
-static bool cont_traj(int64_t B) {
-  const char* e = getenv("IKG_CONT_TRAJ");
-  if (e) return atoi(e) != 0;
-  return B <= kTrajMaxB;
-}
+static bool cont_traj(int64_t B) { return env_flag("IKG_CONT_TRAJ", B <= kTrajMaxB); }
 
 // IKG_TRAJ_FUSE=0: the updates and the scan of a window as separate launches
 // (no overlap of window r + 1's updates with window r's scan)
-static bool traj_fuse() {
-  const char* e = getenv("IKG_TRAJ_FUSE");
-  return !(e && atoi(e) == 0);
-}
+static bool traj_fuse() { return env_flag("IKG_TRAJ_FUSE", true); }
 
 // record window per problem: kTrajWindow iterates per (update, scan) round,
 // fewer (at least 16) when two buffers of Wn records for every problem of the
@@ -2357,29 +2320,23 @@ static hipError_t launch_traj_t(const KModel<T>* dm, const KCollision<T>* dc, co
   const size_t full = (size_t)prm.max_iters + 1;
   const size_t per = 2 * RL * sizeof(T) * B;  // one iterate of every slot, both buffers
   int Wn = (int)std::min({full, (size_t)kTrajWindow, std::max<size_t>(16, kTrajBudget / per)});
-  if (const char* ev = getenv("IKG_TRAJ_WINDOW"))  // timing / test knob
-    Wn = (int)std::min<size_t>(full, (size_t)std::max(16, atoi(ev)));
+  const long long ew = env_int("IKG_TRAJ_WINDOW", LLONG_MIN);  // timing / test knob
+  if (ew != LLONG_MIN) Wn = (int)std::min<size_t>(full, (size_t)std::max(16, (int)ew));
   const int rounds = (int)((full + Wn - 1) / Wn);
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_rec = al(per * Wn), b_q = al(sizeof(T) * nq * B), b_i = al(sizeof(int32_t) * B),
-               b_c = al(sizeof(TrajCert<T>) * B);
-  char* ws = nullptr;
-  hipError_t e = ws_alloc(a.ws_owner, (void**)&ws, b_rec + b_q + 6 * b_i + b_c, s);
+  const TrajLayout l(B, RL * sizeof(T), Wn, sizeof(T) * nq, sizeof(TrajCert<T>));
+  Workspace ws(a.ws_owner, s, "traj");
+  hipError_t e = ws.alloc(l);
   if (e != hipSuccess) return e;
   TrajWs<T> w;
-  char* c = ws;
-  w.rec = (T*)c, c += b_rec;
-  w.qrun = (T*)c, c += b_q;
-  w.itrun = (int32_t*)c, c += b_i;
-  w.it0 = (int32_t*)c, c += 2 * b_i;
-  w.nrec = (int32_t*)c, c += 2 * b_i;
-  w.done = (int32_t*)c, c += b_i;
-  w.cst = (TrajCert<T>*)c;
+  w.rec = ws.at<T>(l.rec);
+  w.qrun = ws.at<T>(l.qrun);
+  w.itrun = ws.at<int32_t>(l.itrun);
+  w.it0 = ws.at<int32_t>(l.it0);
+  w.nrec = ws.at<int32_t>(l.nrec);
+  w.done = ws.at<int32_t>(l.done);
+  w.cst = ws.at<TrajCert<T>>(l.cst);
   w.slots = (int64_t)B;
   w.cert = scan_cert();
-  ws_trace("alloc traj", ws, b_rec + b_q + 6 * b_i + b_c, s);
-  poison_float(w.rec, b_rec + b_q, s);  // records, qrun
-  poison_int(w.itrun, 6 * b_i + b_c, s);  // itrun, it0, nrec, done, cst
   hipLaunchKernelGGL(ikg_fill_i32_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, w.done, a.B, 0);
   const int32_t* wit0 = first ? nullptr : (const int32_t*)cw.wit;
   const int32_t* clist = (const int32_t*)cw.clist;
@@ -2403,10 +2360,7 @@ static hipError_t launch_traj_t(const KModel<T>* dm, const KCollision<T>* dc, co
                        (const T*)a.targets, a.S, clist, cnt, wit0, w, Wn, r, rounds, tblocks, first ? 1 : 0,
                        (T*)a.q_out, a.converged, a.iters, (T*)a.err_out);
   }
-  e = hipGetLastError();
-  ws_trace("free traj", ws, 0, s);
-  const hipError_t ef = ws_free(a.ws_owner, ws, s);
-  return e != hipSuccess ? e : ef;
+  return ws.finish(hipGetLastError());
 }
 
 
@@ -2424,22 +2378,127 @@ __global__ __launch_bounds__(256) void ikg_mark_converged_kernel(const uint8_t* 
 // C2 with the collision term from 1.64 to 1.57 ms, but one in three runs of
 // tests/test_gpu_graph.py gave a replay that differed from the direct solve
 // (cause not found), so it stays an opt-in experiment.
-static bool traj_prescreen(int64_t) {
-  const char* e = getenv("IKG_TRAJ_PRESCREEN");
-  return !(e && atoi(e) == 0);
-}
+static bool traj_prescreen() { return env_flag("IKG_TRAJ_PRESCREEN", true); }
 
 template <typename T, bool DAMPED, class SP>
-static void launch_continue_sel(const KModel<T>* dm, const KCollision<T>* dc, const KParams<T>& prm,
-                                const BatchArgs& a, int nq, int ng, const ContWs<T>& w, hipStream_t s,
-                                hipError_t& err, bool first) {
+static hipError_t launch_continue_sel(const KModel<T>* dm, const KCollision<T>* dc, const KParams<T>& prm,
+                                      const BatchArgs& a, int nq, int ng, const ContWs<T>& w, hipStream_t s,
+                                      bool first) {
   if (cont_traj(a.B)) {
-    err = launch_traj_t<T, DAMPED, SP>(dm, dc, prm, a, nq, w, first, s);
-    if (err != hipErrorOutOfMemory || first) return;
+    const hipError_t err = launch_traj_t<T, DAMPED, SP>(dm, dc, prm, a, nq, w, first, s);
+    if (err != hipErrorOutOfMemory || first) return err;
     (void)hipGetLastError();  // no room for the record buffers: the interleaved continuation needs none
-    err = hipSuccess;
   }
   launch_continue_t<T, DAMPED, SP>(dm, dc, prm, a, nq, ng, w, s);
+  return hipSuccess;
+}
+
+// The records solve: the batch kernel wrote window checkpoints from each
+// problem's first passing iterate (ikg_solve.hpp kWinOf): (1) one wave per
+// problem of the batch checks it there and, when it collides, tests every
+// window's box against a certificate at that iterate (round -2); (2) the
+// problems with a window left are listed; (3) the batch kernel regenerates
+// their records from that window on (resume launch); (4) the records scan
+template <typename T>
+static hipError_t records_solve(const KModel<T>* dm, const KCollision<T>* dc, const KParams<T>& prm,
+                                const BatchArgs& a, int spec, const ContWs<T>& w, hipStream_t s) {
+  const int split = scan_split();
+  const ScanLayout l(a.B, mask_words<T>(prm.max_iters), sizeof(TrajCert<T>), rec_windows<T>(prm.max_iters), split > 0);
+  Workspace ws(a.ws_owner, s, "scan");
+  hipError_t ec = ws.alloc(l);
+  if (ec != hipSuccess) return ec;
+  TrajWs<T> tw{};
+  tw.rec = (T*)a.recs.rec;
+  tw.nrec = a.recs.rec_n;
+  tw.it0 = a.iters;
+  // `done` is only written (read by later rounds, of which there are none here), so it needs no fill
+  tw.done = ws.at<int32_t>(l.done);
+  tw.wmask = ws.at<uint32_t>(l.wmask);
+  tw.cst = ws.at<TrajCert<T>>(l.cst);
+  uint64_t* rmask = ws.at<uint64_t>(l.rmask);
+  tw.rmask = rmask;
+  tw.slots = a.B;
+  tw.by_p = 1;
+  tw.cert = scan_cert();
+  tw.ck = (const T*)a.recs.ck;
+  tw.box = box_cover();
+  tw.split_waves = split;
+  if (split > 0) {
+    tw.best = ws.at<int32_t>(l.best);
+    tw.arrive = ws.at<int32_t>(l.arrive);
+  }
+  tw.wit_out = w.wit;
+  // the problems with windows left are appended to w.clist (count w.count[1])
+  // by the kernels themselves (no compaction launches; the order is the
+  // atomics', and no answer depends on it)
+  TrajWs<T> tf = tw;
+  tf.app_list = w.clist;
+  tf.app_count = w.count + 1;
+  (void)hipMemsetAsync(w.count + 1, 0, 2 * sizeof(int32_t), s);
+  if (first_fused()) {  // one wave per problem of the batch: the first check and the window boxes
+    hipLaunchKernelGGL((ikg_first_check_kernel<T>), dim3((unsigned)std::min<int64_t>(a.B, int64_t(1) << 20)), dim3(64),
+                       0, s, dm, dc, (const T*)a.targets, a.S, a.B, (const int32_t*)nullptr,
+                       (const int32_t*)nullptr, (const int32_t*)nullptr, tf, (T*)a.q_out, a.converged, a.iters,
+                       (T*)a.err_out);
+  } else {  // the pre-screen lists the colliding (w.list, count w.count[2]), the window boxes run over that list
+    hipLaunchKernelGGL((ikg_prescreen_kernel<T>), dim3((unsigned)a.B), dim3(64), 0, s, dm, dc, (const T*)a.q_out,
+                       (const T*)a.targets, a.S, a.B, (const uint8_t*)a.converged, w.wit, w.list, w.count + 2);
+    hipLaunchKernelGGL((ikg_first_check_kernel<T>), dim3((unsigned)scan_waves(a.B)), dim3(64), 0, s, dm, dc,
+                       (const T*)a.targets, a.S, a.B, (const int32_t*)w.list, (const int32_t*)(w.count + 2),
+                       (const int32_t*)w.wit, tf, (T*)a.q_out, a.converged, a.iters, (T*)a.err_out);
+  }
+  // the listed problems' records hold rec_slots problems (ikg_capi.hip
+  // records capacity): the resume kernel and the scan run in rounds of that
+  // many list entries -- launched for every round the batch could need, a
+  // round past the list's end exits at once
+  const int64_t cap = a.recs.rec_slots > 0 ? std::min<int64_t>(a.recs.rec_slots, a.B) : a.B;
+  tw.wit_out = nullptr;
+  for (int64_t rb = 0; rb < a.B && ec == hipSuccess; rb += cap) {
+    BatchArgs r = a;
+    r.rec_list = w.clist;
+    r.rec_count = w.count + 1;
+    r.rec_wmask = tw.wmask;
+    r.rec_rmask = rmask;
+    r.rec_rbase = rb;
+    r.rec_rcap = cap;
+    ec = launch_pair_batch<T>(dm, prm, r, spec, s);
+    if (ec != hipSuccess) break;
+    tw.rbase = rb;
+    tw.rcap = cap;
+    hipLaunchKernelGGL((ikg_traj_scan_kernel<T>), dim3((unsigned)scan_waves(cap)), dim3(64), 0, s, dm, dc,
+                       (const T*)a.targets, a.S, (const int32_t*)w.clist, (const int32_t*)(w.count + 1),
+                       (const int32_t*)w.wit, tw, prm.max_iters + 1, 0, (T*)a.q_out, a.converged, a.iters,
+                       (T*)a.err_out);
+    ec = hipGetLastError();
+  }
+  return ws.finish(ec);
+}
+
+// Pre-screen, compaction and continuation (the trajectory windows, or the
+// interleaved continuation).  Without a pre-screen the trajectory
+// continuation's first launch runs the first checks, so every converged
+// problem is listed.
+template <typename T>
+static hipError_t prescreen_continue(const KModel<T>* dm, const KCollision<T>* dc, const KParams<T>& prm,
+                                     const BatchArgs& a, int spec, int nq, int ng, const ContWs<T>& w,
+                                     hipStream_t s) {
+  const bool first = cont_traj(a.B) && !traj_prescreen();
+  if (first)
+    hipLaunchKernelGGL(ikg_mark_converged_kernel, dim3((unsigned)((a.B + 255) / 256)), dim3(256), 0, s,
+                       (const uint8_t*)a.converged, a.B, w.wit);
+  else
+    hipLaunchKernelGGL((ikg_prescreen_kernel<T>), dim3((unsigned)a.B), dim3(64), 0, s, dm, dc, (const T*)a.q_out,
+                       (const T*)a.targets, a.S, a.B, (const uint8_t*)a.converged, w.wit);
+  // listed: witness >= 0 (the chunk counts borrow the stretch list, written only after)
+  const unsigned nb = (unsigned)((a.B + kCompactChunk - 1) / kCompactChunk);
+  hipLaunchKernelGGL(ikg_compact_count_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)w.wit, a.B, w.list);
+  hipLaunchKernelGGL(ikg_compact_write_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)w.wit, a.B,
+                     (const int32_t*)w.list, w.clist, w.count + 1);
+  hipError_t ec = hipSuccess;
+  by_spec(spec, prm.lambda > T(0), [&](auto D, auto sp) {
+    ec = launch_continue_sel<T, decltype(D)::value, decltype(sp)>(dm, dc, prm, a, nq, ng, w, s, first);
+  });
+  return ec;
 }
 
 template <typename T>
@@ -2448,139 +2507,15 @@ hipError_t launch_collide_continue(const KModel<T>* dm, const KCollision<T>* dc,
   if (a.B <= 0) return hipSuccess;
   if (a.B > 0x7fffffff) return hipErrorInvalidValue;
   // stream-ordered workspace: the pre-screen's witness pair per problem
-  const size_t ib = ((sizeof(int32_t) * (size_t)a.B + 255) & ~(size_t)255);
-  char* ws = nullptr;
-  hipError_t e = ws_alloc(a.ws_owner, (void**)&ws, 3 * ib + 256 + sizeof(T) * kStretchRec * (size_t)a.B, s);
+  const ContLayout l(a.B, sizeof(T) * kStretchRec);
+  Workspace ws(a.ws_owner, s, "cont");
+  const hipError_t e = ws.alloc(l);
   if (e != hipSuccess) return e;
-  ContWs<T> w{(int32_t*)ws, (int32_t*)(ws + ib), (int32_t*)(ws + 3 * ib), (int32_t*)(ws + 2 * ib),
-              (T*)(ws + 3 * ib + 256)};
-  ws_trace("alloc cont", ws, 3 * ib + 256 + sizeof(T) * kStretchRec * (size_t)a.B, s);
-  poison_int(ws, 3 * ib + 256, s);  // witness, lists, counts
-  poison_float(w.rec, sizeof(T) * kStretchRec * (size_t)a.B, s);
-  const bool damped = prm.lambda > T(0);
-  hipError_t ec = hipSuccess;
-  const unsigned nb = (unsigned)((a.B + kCompactChunk - 1) / kCompactChunk);
-  auto compact = [&] {  // listed: witness >= 0 (the chunk counts borrow the stretch list, written only after)
-    hipLaunchKernelGGL(ikg_compact_count_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)w.wit, a.B, w.list);
-    hipLaunchKernelGGL(ikg_compact_write_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)w.wit, a.B,
-                       (const int32_t*)w.list, w.clist, w.count + 1);
-  };
-  if (a.rec_used && *a.rec_used) {
-    // the batch kernel wrote window checkpoints from each problem's first
-    // passing iterate (ikg_solve.hpp kWinOf): (1) one wave per problem of the
-    // batch checks it there and, when it collides, tests every window's box
-    // against a certificate at that iterate (round -2); (2) the problems with
-    // a window left are listed; (3) the batch kernel regenerates their
-    // records from that window on (resume launch); (4) the records scan
-    const size_t bi = ((sizeof(int32_t) * (size_t)a.B + 255) & ~(size_t)255);
-    const size_t bm = ((sizeof(uint32_t) * (size_t)mask_words<T>(prm.max_iters) * (size_t)a.B + 255) & ~(size_t)255);
-    const size_t bc = ((sizeof(TrajCert<T>) * (size_t)a.B + 255) & ~(size_t)255);
-    const size_t br = ((sizeof(uint64_t) * (size_t)rec_windows<T>(prm.max_iters) * (size_t)a.B + 255) & ~(size_t)255);
-    char* dws = nullptr;
-    e = ws_alloc(a.ws_owner, (void**)&dws, bi + bm + bc + br + 2 * bi, s);
-    if (e != hipSuccess) return e;
-    TrajWs<T> tw{};
-    tw.rec = (T*)a.rec;
-    tw.nrec = a.rec_n;
-    tw.it0 = a.iters;
-    tw.done = (int32_t*)dws;
-    tw.wmask = (uint32_t*)(dws + bi);
-    tw.cst = (TrajCert<T>*)(dws + bi + bm);
-    uint64_t* rmask = (uint64_t*)(dws + bi + bm + bc);
-    tw.rmask = rmask;
-    tw.slots = a.B;
-    tw.by_p = 1;
-    tw.cert = scan_cert();
-    tw.ck = (const T*)a.ck;
-    tw.box = box_cover();
-    tw.split_waves = scan_split();
-    if (tw.split_waves > 0) {
-      tw.best = (int32_t*)(dws + bi + bm + bc + br);
-      tw.arrive = (int32_t*)(dws + bi + bm + bc + br + bi);
-    }
-    ws_trace("alloc scan", dws, bi + bm + bc + br + 2 * bi, s);
-    poison_int(dws, bi + bm + bc, s);
-    poison_int(rmask, br, s);
-    if (tw.best) poison_int(tw.best, 2 * bi, s);  // the first check sets them for every problem it may list
-    // `done` is only written (read by later rounds, of which there are none here), so it needs no fill
-    tw.wit_out = w.wit;
-    // the problems with windows left are appended to w.clist (count w.count[1])
-    // by the kernels themselves (no compaction launches; the order is the
-    // atomics', and no answer depends on it)
-    TrajWs<T> tf = tw;
-    tf.app_list = w.clist;
-    tf.app_count = w.count + 1;
-    (void)hipMemsetAsync(w.count + 1, 0, 2 * sizeof(int32_t), s);
-    if (first_fused(a.B)) {  // one wave per problem of the batch: the first check and the window boxes
-      hipLaunchKernelGGL((ikg_first_check_kernel<T>), dim3((unsigned)std::min<int64_t>(a.B, int64_t(1) << 20)), dim3(64),
-                         0, s, dm, dc, (const T*)a.targets, a.S, a.B, (const int32_t*)nullptr,
-                         (const int32_t*)nullptr, (const int32_t*)nullptr, tf, (T*)a.q_out, a.converged, a.iters,
-                         (T*)a.err_out);
-    } else {  // the pre-screen lists the colliding (w.list, count w.count[2]), the window boxes run over that list
-      hipLaunchKernelGGL((ikg_prescreen_kernel<T>), dim3((unsigned)a.B), dim3(64), 0, s, dm, dc, (const T*)a.q_out,
-                         (const T*)a.targets, a.S, a.B, (const uint8_t*)a.converged, w.wit, w.list, w.count + 2);
-      hipLaunchKernelGGL((ikg_first_check_kernel<T>), dim3((unsigned)scan_waves(a.B)), dim3(64), 0, s, dm, dc,
-                         (const T*)a.targets, a.S, a.B, (const int32_t*)w.list, (const int32_t*)(w.count + 2),
-                         (const int32_t*)w.wit, tf, (T*)a.q_out, a.converged, a.iters, (T*)a.err_out);
-    }
-    // the listed problems' records hold rec_slots problems (ikg_capi.hip
-    // records capacity): the resume kernel and the scan run in rounds of that
-    // many list entries -- launched for every round the batch could need, a
-    // round past the list's end exits at once
-    const int64_t cap = a.rec_slots > 0 ? std::min<int64_t>(a.rec_slots, a.B) : a.B;
-    tw.wit_out = nullptr;
-    for (int64_t rb = 0; rb < a.B && ec == hipSuccess; rb += cap) {
-      BatchArgs r = a;
-      r.rec_list = w.clist;
-      r.rec_count = w.count + 1;
-      r.rec_wmask = tw.wmask;
-      r.rec_rmask = rmask;
-      r.rec_rbase = rb;
-      r.rec_rcap = cap;
-      ec = launch_pair_batch<T>(dm, prm, r, spec, s);
-      if (ec != hipSuccess) break;
-      tw.rbase = rb;
-      tw.rcap = cap;
-      hipLaunchKernelGGL((ikg_traj_scan_kernel<T>), dim3((unsigned)scan_waves(cap)), dim3(64), 0, s, dm, dc,
-                         (const T*)a.targets, a.S, (const int32_t*)w.clist, (const int32_t*)(w.count + 1),
-                         (const int32_t*)w.wit, tw, prm.max_iters + 1, 0, (T*)a.q_out, a.converged, a.iters,
-                         (T*)a.err_out);
-      ec = hipGetLastError();
-    }
-    ws_trace("free scan", dws, 0, s);
-    const hipError_t ef2 = ws_free(a.ws_owner, dws, s);
-    if (ec == hipSuccess) ec = ef2;
-    e = ec != hipSuccess ? ec : hipGetLastError();
-    ws_trace("free cont", ws, 0, s);
-    const hipError_t ef = ws_free(a.ws_owner, ws, s);
-    return e != hipSuccess ? e : ef;
-  }
-  // trajectory continuation without a pre-screen: the first checks run in its
-  // first launch, so every converged problem is listed
-  const bool first = cont_traj(a.B) && !traj_prescreen(a.B);
-  if (first)
-    hipLaunchKernelGGL(ikg_mark_converged_kernel, dim3((unsigned)((a.B + 255) / 256)), dim3(256), 0, s,
-                       (const uint8_t*)a.converged, a.B, w.wit);
-  else
-    hipLaunchKernelGGL((ikg_prescreen_kernel<T>), dim3((unsigned)a.B), dim3(64), 0, s, dm, dc, (const T*)a.q_out,
-                       (const T*)a.targets, a.S, a.B, (const uint8_t*)a.converged, w.wit);
-  compact();
-  if (spec == kSpecNextage) {
-    if (damped)
-      launch_continue_sel<T, true, SpecNextage>(dm, dc, prm, a, nq, ng, w, s, ec, first);
-    else
-      launch_continue_sel<T, false, SpecNextage>(dm, dc, prm, a, nq, ng, w, s, ec, first);
-  } else if (damped) {
-    launch_continue_sel<T, true, SpecGeneric>(dm, dc, prm, a, nq, ng, w, s, ec, first);
-  } else if (spec == kSpecGenericWrist) {
-    launch_continue_sel<T, false, SpecGenericWrist>(dm, dc, prm, a, nq, ng, w, s, ec, first);
-  } else {
-    launch_continue_sel<T, false, SpecGeneric>(dm, dc, prm, a, nq, ng, w, s, ec, first);
-  }
-  e = ec != hipSuccess ? ec : hipGetLastError();
-  ws_trace("free cont", ws, 0, s);
-  const hipError_t ef = ws_free(a.ws_owner, ws, s);
-  return e != hipSuccess ? e : ef;
+  const ContWs<T> w{ws.at<int32_t>(l.wit), ws.at<int32_t>(l.list), ws.at<int32_t>(l.count), ws.at<int32_t>(l.clist),
+                    ws.at<T>(l.rec)};
+  const hipError_t ec = a.recs.rec_used && *a.recs.rec_used ? records_solve<T>(dm, dc, prm, a, spec, w, s)
+                                                            : prescreen_continue<T>(dm, dc, prm, a, spec, nq, ng, w, s);
+  return ws.finish(ec != hipSuccess ? ec : hipGetLastError());
 }
 
 #ifdef IKG_CPROF

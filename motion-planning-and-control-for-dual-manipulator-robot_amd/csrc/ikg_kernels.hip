@@ -220,19 +220,15 @@ __global__ __launch_bounds__(256) void ikg_log6_kernel(const T* __restrict__ M, 
 // single-wave workgroup, which caps how many workgroups the dispatcher packs
 // onto one CU.
 static size_t lds_pad_bytes() {
-  static long v = -1;
-  if (v < 0) {
-    const char* e = getenv("IKG_LDS_PAD");
-    v = e ? atol(e) : 0;
-  }
-  return (size_t)v;
+  static const size_t v = (size_t)env_int("IKG_LDS_PAD", 0);
+  return v;
 }
 
 static int64_t packed_min_batch();
 
 // IKG_PAIR_ILP=0: the default-scheduled pair kernel for every launch (A/B knob)
 static bool pair_ilp_on() {
-  static const bool v = !(getenv("IKG_PAIR_ILP") && atoi(getenv("IKG_PAIR_ILP")) == 0);
+  static const bool v = env_flag("IKG_PAIR_ILP", true);
   return v;
 }
 
@@ -241,7 +237,7 @@ static void launch_pair_batch_t(const KModel<T>* dmodel, const KParams<T>& prm, 
   const int ppw = a.ppw;
   const dim3 grid((unsigned)((a.B + ppw - 1) / ppw));
   // IKG_FORCE_MED=1: measurement knob, the inline medium-range rule for every launch
-  static const bool force_med = getenv("IKG_FORCE_MED") && atoi(getenv("IKG_FORCE_MED")) != 0;
+  static const bool force_med = env_flag("IKG_FORCE_MED", false);
   // per-problem seeds (multi-start, or a q0 row per target): large first steps
   // are common, so the frame-1 loop takes the medium-range trig rule inline.
   // fp64 with a broadcast q0 keeps the short-series rule (exact sincos beyond
@@ -253,15 +249,15 @@ static void launch_pair_batch_t(const KModel<T>* dmodel, const KParams<T>& prm, 
     // fp32, no records, at most one wave per SIMD: the max-ILP build of the
     // same kernel (ikg_pair_ilp.hip)
     if constexpr (std::is_same<SP, SpecNextage>::value && std::is_same<T, float>::value)
-      if (!a.rec && pair_ilp_on() && (int64_t)grid.x * 32 < packed_min_batch()) {
+      if (!a.recs.rec && pair_ilp_on() && (int64_t)grid.x * 32 < packed_min_batch()) {
         (void)launch_pair_ilp(dmodel, prm, a, med, lds_pad_bytes(), s);
         return;
       }
-    if (a.rec) {  // collision continuation checkpoints (ikg_collision.hip), one fixed slot per problem
+    if (a.recs.rec) {  // collision continuation checkpoints (ikg_collision.hip), one fixed slot per problem
       RecArgs<T> ra;
-      ra.rec = (T*)a.rec;
-      ra.nrec = a.rec_n;
-      ra.ck = (T*)a.ck;
+      ra.rec = (T*)a.recs.rec;
+      ra.nrec = a.recs.rec_n;
+      ra.ck = (T*)a.recs.ck;
       ra.list = a.rec_list;
       ra.count = a.rec_count;
       ra.wmask = a.rec_wmask;
@@ -288,7 +284,7 @@ static void launch_pair_batch_t(const KModel<T>* dmodel, const KParams<T>& prm, 
       } else {
         go(ikg_pair_batch_kernel<T, DAMPED, SP, false, 1>);
       }
-      if (a.rec_used) *a.rec_used = true;
+      if (a.recs.rec_used) *a.recs.rec_used = true;
       return;
     }
     if (med) {
@@ -343,12 +339,9 @@ bool quad_applies(const KParams<T>& prm, int spec) {
 }
 
 static int64_t quad_max_batch() {
-  static long v = -1;
-  if (v < 0) {
-    const char* e = getenv("IKG_QUAD_MAX_BATCH");
-    v = e ? atol(e) : 0;  // measured no faster than PAIR: explicit variant only
-  }
-  return (int64_t)v;
+  // measured no faster than PAIR: explicit variant only
+  static const int64_t v = env_int("IKG_QUAD_MAX_BATCH", 0);
+  return v;
 }
 
 // The layout a launch of B problems runs (AUTO resolved; PAIR also stands for
@@ -360,7 +353,7 @@ int resolve_variant(const KParams<T>& prm, int spec, int variant, int64_t B, boo
   if (variant == IKG_VARIANT_QUAD || (variant == IKG_VARIANT_AUTO && B <= quad_max_batch()))
     if (quad_applies(prm, spec)) return IKG_VARIANT_QUAD;
   if constexpr (std::is_same<T, float>::value) {
-    static const bool rec_pair = getenv("IKG_REC_PREFER_PAIR") && atoi(getenv("IKG_REC_PREFER_PAIR")) != 0;
+    static const bool rec_pair = env_flag("IKG_REC_PREFER_PAIR", false);
     const bool want = variant == IKG_VARIANT_PACKED ||
                       (variant == IKG_VARIANT_AUTO && B >= packed_min_batch() && !(rec_pair && rec));
     if (want && packed_applies(prm, spec)) return IKG_VARIANT_PACKED;
@@ -372,7 +365,7 @@ template <typename T>
 hipError_t launch_pair_batch(const KModel<T>* dmodel, const KParams<T>& prm, const BatchArgs& a, int spec,
                              hipStream_t s) {
   if (a.B <= 0) return hipSuccess;
-  const int v = resolve_variant(prm, spec, a.variant, a.B, a.rec != nullptr);
+  const int v = resolve_variant(prm, spec, a.variant, a.B, a.recs.rec != nullptr);
   if (v == IKG_VARIANT_QUAD) return launch_quad_batch<T>(dmodel, prm, a, s);
   if (a.variant == IKG_VARIANT_QUAD) return hipErrorInvalidValue;  // checked by the C-ABI first
   if constexpr (std::is_same<T, float>::value)
@@ -395,18 +388,9 @@ hipError_t launch_pair_batch(const KModel<T>* dmodel, const KParams<T>& prm, con
     const unsigned grid = (unsigned)((a.B + ppw - 1) / ppw);
     return hipModuleLaunchKernel(f, grid, 1, 1, 64, 1, 1, (unsigned)lds_pad_bytes(), s, args, nullptr);
   }
-  if (spec == kSpecNextage) {
-    if (damped)
-      launch_pair_batch_t<T, true, SpecNextage>(dmodel, prm, a, s);
-    else
-      launch_pair_batch_t<T, false, SpecNextage>(dmodel, prm, a, s);
-  } else if (damped) {  // the damped solve does not use the wrist structure
-    launch_pair_batch_t<T, true, SpecGeneric>(dmodel, prm, a, s);
-  } else if (spec == kSpecGenericWrist) {
-    launch_pair_batch_t<T, false, SpecGenericWrist>(dmodel, prm, a, s);
-  } else {
-    launch_pair_batch_t<T, false, SpecGeneric>(dmodel, prm, a, s);
-  }
+  by_spec(spec, damped, [&](auto D, auto sp) {
+    launch_pair_batch_t<T, decltype(D)::value, decltype(sp)>(dmodel, prm, a, s);
+  });
   return hipGetLastError();
 }
 
@@ -420,11 +404,7 @@ hipError_t launch_multistart(const KModel<T>* dmodel, const KParams<T>& prm, con
   BatchArgs b{a.targets, a.seeds, a.S == 1 ? 0 : a.nq, a.T * a.S, a.ws_q, a.ws_conv, a.ws_iters, a.ws_err, 32, a.S};
   b.ws_owner = a.ws_owner;
   b.jit = a.jit;
-  b.rec = a.rec;
-  b.rec_n = a.rec_n;
-  b.ck = a.ck;
-  b.rec_slots = a.rec_slots;
-  b.rec_used = a.rec_used;
+  b.recs = a.recs;
   // AUTO keeps the pair layout here: seeds spread the update counts, and a
   // wave lasts as long as its slowest problem -- 64 per packed wave against 32
   // per pair wave measured 4.17 ms against 3.66 ms (256 seeds x 512 targets,
@@ -432,7 +412,7 @@ hipError_t launch_multistart(const KModel<T>* dmodel, const KParams<T>& prm, con
   b.variant = a.variant == IKG_VARIANT_AUTO ? IKG_VARIANT_PAIR : a.variant;
   // with collision records: rec_chunk targets (and their S seeds) per launch,
   // so the records' fixed slots fit the budget (ikg_capi.hip rec_chunk)
-  const int64_t tc = a.rec && a.rec_chunk > 0 ? a.rec_chunk : a.T;
+  const int64_t tc = a.recs.rec && a.rec_chunk > 0 ? a.rec_chunk : a.T;
   for (int64_t t0 = 0; t0 < a.T; t0 += tc) {
     BatchArgs c = b;
     const int64_t nt = std::min(tc, a.T - t0);

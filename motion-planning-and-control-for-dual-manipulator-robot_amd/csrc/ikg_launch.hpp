@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -16,10 +17,21 @@
 #include "ikg_device.hpp"
 #include "ikg_dynamics.hpp"
 #include "ikg_solve.hpp"
+#include "ikg_ws_layout.hpp"
 
 namespace ikg {
 
 struct JitKernels;  // ikg_jit.hpp
+
+// Runtime knobs.  env_int reads the environment afresh at every call.  A knob
+// read once per process says so where it is read (`static const ... =
+// env_int(...)`); every other knob is read per launch, so one process (the
+// tests) can flip it between solves.
+inline long long env_int(const char* name, long long dflt) {
+  const char* e = getenv(name);
+  return e ? atoll(e) : dflt;
+}
+inline bool env_flag(const char* name, bool dflt) { return env_int(name, dflt) != 0; }
 
 // Workspaces of captured solves.  Outside a stream capture a
 // solve's scratch is stream-ordered: hipMallocAsync / hipFreeAsync.  Inside a
@@ -147,10 +159,7 @@ inline void* ws_take_pending(WsState& st, int dev, size_t bytes, size_t* got, hi
 // (profiles/r06/records/; round 5 kept 6.5 GiB).
 // IKG_WS_KEEP_MB overrides (0 = keep nothing, as the device's default pool).
 inline uint64_t ws_keep_bytes() {
-  static const uint64_t v = [] {
-    const char* e = getenv("IKG_WS_KEEP_MB");
-    return e ? (uint64_t)strtoull(e, nullptr, 10) << 20 : (uint64_t)1280 << 20;
-  }();
+  static const uint64_t v = (uint64_t)env_int("IKG_WS_KEEP_MB", 1280) << 20;
   return v;
 }
 
@@ -163,7 +172,7 @@ inline uint64_t ws_keep_bytes() {
 // ikg_model_destroy destroys them (ws_pool_release).  IKG_WS_POOL=0: the
 // device's default pool (A/B).
 inline hipMemPool_t ws_pool(WsOwner* owner) {
-  static const bool on = !(getenv("IKG_WS_POOL") && atoi(getenv("IKG_WS_POOL")) == 0);
+  static const bool on = env_flag("IKG_WS_POOL", true);
   if (!on || !owner) return nullptr;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= WsState::kDevs) return nullptr;
@@ -308,6 +317,83 @@ inline hipError_t ws_free(WsOwner* owner, void* p, hipStream_t s) {
   return hipFreeAsync(p, s);
 }
 
+// Debug knob IKG_WS_TRACE=1: every stream-ordered workspace allocation and
+// free is printed (address range, whether the stream is capturing).
+inline void ws_trace(const char* verb, const char* name, const void* p, size_t bytes, hipStream_t s) {
+  if (!env_flag("IKG_WS_TRACE", false)) return;
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(s, &st);
+  fprintf(stderr, "[ikg ws] %s %s %p +%zu -> %p%s\n", verb, name, p, bytes, (const void*)((const char*)p + bytes),
+          st == hipStreamCaptureStatusActive ? " (capturing)" : "");
+}
+
+// One stream-ordered workspace: laid out by a WsLayout, allocated and traced
+// once, and freed on every path out of its scope.  release() (or finish) hands
+// back the free's error for the callers that report it.
+// Debug knob IKG_POISON=1: the arrays are filled by their tags right after the
+// allocation (adjacent arrays of one tag in one fill), so a read of memory the
+// solve did not write gives a wrong answer on the first run instead of stale
+// data from an earlier solve or graph replay.
+class Workspace {
+ public:
+  Workspace(WsOwner* owner, hipStream_t s, const char* name) : owner_(owner), s_(s), name_(name) {}
+  Workspace(const Workspace&) = delete;
+  Workspace& operator=(const Workspace&) = delete;
+  ~Workspace() { (void)release(); }
+
+  hipError_t alloc(const WsLayout& l) {
+    const hipError_t e = ws_alloc(owner_, (void**)&base_, l.total, s_);
+    if (e != hipSuccess) {
+      base_ = nullptr;  // (a capture that could not keep the buffer has queued it for the next drain)
+      return e;
+    }
+    lay_ = l;
+    ws_trace("alloc", name_, base_, l.total, s_);
+    if (!env_flag("IKG_POISON", false)) return hipSuccess;
+    for (int i = 0, j; i < l.n; i = j) {
+      size_t end = l.off[i] + l.len[i];
+      for (j = i + 1; j < l.n && l.fill[j] == l.fill[i] && l.off[j] == end; ++j) end += l.len[j];
+      if (l.fill[i] != WsLayout::kNoFill && end > l.off[i])
+        (void)hipMemsetAsync(base_ + l.off[i], l.fill[i] == WsLayout::kInt ? 0xFF : 0x7F, end - l.off[i], s_);
+    }
+    return hipSuccess;
+  }
+  explicit operator bool() const { return base_ != nullptr; }
+  template <typename U>
+  U* at(int i) const {
+    return (U*)(base_ + lay_.off[i]);
+  }
+  hipError_t release() {
+    if (!base_) return hipSuccess;
+    ws_trace("free", name_, base_, 0, s_);
+    char* p = base_;
+    base_ = nullptr;
+    return ws_free(owner_, p, s_);
+  }
+  // what a launcher returns: its launch error first, then the free's
+  hipError_t finish(hipError_t e) {
+    const hipError_t ef = release();
+    return e != hipSuccess ? e : ef;
+  }
+
+ private:
+  WsOwner* owner_;
+  hipStream_t s_;
+  const char* name_;
+  char* base_ = nullptr;
+  WsLayout lay_;
+};
+
+// Collision continuation: the buffers offered to the pair kernel, which
+// records every iterate from the first passing one on (RecOut)
+struct RecBufs {
+  void* rec = nullptr;
+  int32_t* rec_n = nullptr;
+  void* ck = nullptr;         // window checkpoints (ikg_solve.hpp kWinOf), ck_per_problem per problem
+  bool* rec_used = nullptr;   // set when the launch took them
+  int64_t rec_slots = 0;      // records capacity: problems whose records `rec` holds (0: every problem of the launch)
+};
+
 struct BatchArgs {
   const void* targets;
   const void* q0;
@@ -322,13 +408,7 @@ struct BatchArgs {
   int variant = 0; // ikg_variant
   // model-specialised pair kernels on this device (ikg_model_specialize), or null
   const JitKernels* jit = nullptr;
-  // collision continuation: record buffers offered to the pair kernel (records
-  // every iterate from the first passing one on, RecOut); `rec_used` is set
-  // when the launch took them
-  void* rec = nullptr;
-  int32_t* rec_n = nullptr;
-  void* ck = nullptr;           // window checkpoints (ikg_solve.hpp kWinOf), ck_per_problem per problem
-  bool* rec_used = nullptr;
+  RecBufs recs;
   // resume launch (the collision scan's windows to regenerate, ikg_collision.hip):
   // listed problems, their count (device) and windows to regenerate per problem
   const int32_t* rec_list = nullptr;
@@ -336,7 +416,6 @@ struct BatchArgs {
   const uint32_t* rec_wmask = nullptr;
   uint64_t* rec_rmask = nullptr;    // per problem and window, the iterates the resume kernel recorded
   int64_t rec_rbase = 0, rec_rcap = 0;  // list entries [rbase, rbase + rcap) this resume launch regenerates
-  int64_t rec_slots = 0;        // records capacity: problems whose records `rec` holds (0: every problem of the launch)
   WsOwner* ws_owner = nullptr;  // scratch of captured solves (ws_alloc)
 };
 
@@ -369,48 +448,32 @@ struct MultiArgs {
   int variant = 0;  // ikg_variant of the per-seed solves
   const JitKernels* jit = nullptr;
   WsOwner* ws_owner = nullptr;
-  // collision continuation records for the S x T per-seed problems (BatchArgs::rec)
-  void* rec = nullptr;
-  int32_t* rec_n = nullptr;
-  void* ck = nullptr;
-  bool* rec_used = nullptr;
-  int64_t rec_slots = 0;  // BatchArgs::rec_slots
+  RecBufs recs;           // for the S x T per-seed problems (BatchArgs::recs)
   int64_t rec_chunk = 0;  // targets per launch when the records of all T x S problems exceed the budget (0: all)
 };
-
-// Debug knob IKG_POISON=1 (read per call): every stream-ordered workspace is
-// filled right after its allocation, so a read of memory the solve did not
-// write gives a wrong answer on the first run instead of stale data from an
-// earlier solve or graph replay.  Integer arrays (counts, indices, flags) get
-// 0xFF bytes (-1: "nothing recorded", never an index that is used); floating
-// arrays get 0x7F bytes (1.4e306 / 3.4e38: finite, so no -ffinite-math-only
-// code sees a NaN, but absurd as a joint angle or an error norm).
-inline bool ws_poison() {
-  const char* e = getenv("IKG_POISON");
-  return e && atoi(e) != 0;
-}
-inline void poison_int(void* p, size_t bytes, hipStream_t s) {
-  if (p && bytes && ws_poison()) (void)hipMemsetAsync(p, 0xFF, bytes, s);
-}
-inline void poison_float(void* p, size_t bytes, hipStream_t s) {
-  if (p && bytes && ws_poison()) (void)hipMemsetAsync(p, 0x7F, bytes, s);
-}
-
-// Debug knob IKG_WS_TRACE=1: every stream-ordered workspace allocation and
-// free is printed (address range, whether the stream is capturing).
-inline void ws_trace(const char* what, const void* p, size_t bytes, hipStream_t s) {
-  const char* e = getenv("IKG_WS_TRACE");
-  if (!(e && atoi(e) != 0)) return;
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(s, &st);
-  fprintf(stderr, "[ikg ws] %s %p +%zu -> %p%s\n", what, p, bytes, (const void*)((const char*)p + bytes),
-          st == hipStreamCaptureStatusActive ? " (capturing)" : "");
-}
 
 // kernel specialisation chosen at model creation (ikg_model_build.hpp)
 constexpr int kSpecGeneric = 0;
 constexpr int kSpecNextage = 1;
 constexpr int kSpecGenericWrist = 2;  // generic tables, spherical-wrist solve
+
+// f(DAMPED constant, Spec value) for the loop that a model's specialisation and
+// the damping select; the damped solve does not use the wrist structure
+template <typename F>
+void by_spec(int spec, bool damped, F&& f) {
+  if (spec == kSpecNextage) {
+    if (damped)
+      f(std::true_type{}, SpecNextage{});
+    else
+      f(std::false_type{}, SpecNextage{});
+  } else if (damped) {
+    f(std::true_type{}, SpecGeneric{});
+  } else if (spec == kSpecGenericWrist) {
+    f(std::false_type{}, SpecGenericWrist{});
+  } else {
+    f(std::false_type{}, SpecGeneric{});
+  }
+}
 
 template <typename T>
 hipError_t launch_pair_batch(const KModel<T>* dmodel, const KParams<T>& prm, const BatchArgs& a, int spec,

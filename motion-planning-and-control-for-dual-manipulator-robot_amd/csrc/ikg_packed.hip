@@ -132,12 +132,8 @@ void ikg_packed_batch_kernel(const KModel<float>* __restrict__ m,
 // Experiment knob (tools/dvfs_probe.py): dynamic LDS reserved per single-wave
 // workgroup, which caps how many workgroups the dispatcher may put on one CU.
 static size_t packed_lds_pad() {
-  static long v = -1;
-  if (v < 0) {
-    const char* e = getenv("IKG_PACKED_LDS_PAD");
-    v = e ? atol(e) : 0;
-  }
-  return (size_t)v;
+  static const size_t v = (size_t)env_int("IKG_PACKED_LDS_PAD", 0);
+  return v;
 }
 
 // SIMDs of the current device (4 per CU), cached per device
@@ -180,9 +176,9 @@ hipError_t launch_packed_batch(const KModel<float>* dmodel, const KParams<float>
   const unsigned simds = simd_count();
   const unsigned need = (grid.x + simds - 1) / simds;  // waves per SIMD the launch needs
   RecArgs<float> ra;
-  ra.rec = (float*)a.rec;
-  ra.nrec = a.rec_n;
-  ra.ck = (float*)a.ck;
+  ra.rec = (float*)a.recs.rec;
+  ra.nrec = a.recs.rec_n;
+  ra.ck = (float*)a.recs.ck;
   ra.list = a.rec_list;
   ra.count = a.rec_count;
   ra.wmask = a.rec_wmask;
@@ -199,7 +195,7 @@ hipError_t launch_packed_batch(const KModel<float>* dmodel, const KParams<float>
 #ifndef IKG_PACKED_REC
 #define IKG_PACKED_REC 1
 #endif
-  if (IKG_PACKED_REC && a.rec) {  // collision continuation checkpoints (0: A/B knob, the trajectory kernel instead)
+  if (IKG_PACKED_REC && a.recs.rec) {  // collision continuation checkpoints (0: A/B knob, the trajectory kernel instead)
     // the resume launch (a.rec_list, REC = 2) takes the cap the batch launch took (need from a.B)
     if (need == 1 && capped_ok<1, 1>())
       a.rec_list ? go(ikg_packed_batch_kernel<SpecNextage, 1, true, 2>) : go(ikg_packed_batch_kernel<SpecNextage, 1, true, 1>);
@@ -207,7 +203,7 @@ hipError_t launch_packed_batch(const KModel<float>* dmodel, const KParams<float>
       a.rec_list ? go(ikg_packed_batch_kernel<SpecNextage, 2, true, 2>) : go(ikg_packed_batch_kernel<SpecNextage, 2, true, 1>);
     else
       a.rec_list ? go(ikg_packed_batch_kernel<SpecNextage, 0, true, 2>) : go(ikg_packed_batch_kernel<SpecNextage, 0, true, 1>);
-    if (a.rec_used) *a.rec_used = true;
+    if (a.recs.rec_used) *a.recs.rec_used = true;
     return hipGetLastError();
   }
   // the medium-range trig rule inline for every launch (and every q0 layout,
