@@ -230,6 +230,10 @@ IKG_HD inline bool wave_any(bool b) {
 #endif
   return b;
 }
+// COLD (the record-free frame-1 pair loop): the branch is laid out off the
+// common path, which then falls through it; a taken branch costs a lone wave ~20 cycles.
+// A macro: the hint is read where it is the branch's own condition, not through a call.
+#define IKG_RARELY(COLD, c) ((COLD) ? __builtin_expect((c), false) : (c))
 IKG_HD inline bool mnot(bool m) { return !m; }
 IKG_HD inline v2i mnot(v2i m) { return m == 0; }
 IKG_HD inline bool mor(bool a, bool b) { return a || b; }
@@ -755,7 +759,7 @@ IKG_HD inline T atan2_upper(T y, T x) {
   return vsel<T>(x < T(0), T(3.14159274f) - r, r);
 }
 
-template <typename T>
+template <typename T, bool COLD = false>
 IKG_HD inline void log6_iter(const T* R, const T* p, T* e, ThetaTrack<T>* tk = nullptr, bool resync = true) {
   using M = typename LaneT<T>::M;
   const T pi = T(Prec<T>::kPi);
@@ -766,7 +770,7 @@ IKG_HD inline void log6_iter(const T* R, const T* p, T* e, ThetaTrack<T>* tk = n
   T theta = T(0);
   if constexpr (is_f64<T>) {
     bool exact = true;
-    if (tk && !resync) {
+    if (tk && (COLD ? __builtin_expect(!resync, true) : !resync)) {
       const T y = st * tk->ct - ct * tk->st;  // rho sin(theta - theta_prev)
       const T x = ct * tk->ct + st * tk->st;  // rho cos(theta - theta_prev)
 #if IKG_THETA_ASIN
@@ -779,7 +783,7 @@ IKG_HD inline void log6_iter(const T* R, const T* p, T* e, ThetaTrack<T>* tk = n
       theta = tk->th + ThetaInc<T>::atan_small(fdiv<T>(y, fmax(x, T(1e-30))));
 #endif
     }
-    if (wave_any<T>(exact)) {
+    if (IKG_RARELY(COLD, wave_any<T>(exact))) {
 #if IKG_THETA == 1
       const T th_x = atan2(st, ct);
 #else
@@ -817,7 +821,7 @@ IKG_HD inline void log6_iter(const T* R, const T* p, T* e, ThetaTrack<T>* tk = n
   // cancellation below the near-pi band (there |1+cos| >= 5e-5: < 2e-14 abs.)
   T alpha = hf * (T(1) + ct);
   const M near_pi = theta >= pi - T(1e-2);
-  if (wave_any<T>(any_of(near_pi))) {  // near pi (rare): the axis from the diagonal
+  if (IKG_RARELY(COLD, wave_any<T>(any_of(near_pi)))) {  // near pi (rare): the axis from the diagonal
     const T beta = fdiv<T>(t2, T(1) - ct);
     const T t0 = (R[0] - ct) * beta, t1 = (R[4] - ct) * beta, tt = (R[8] - ct) * beta;
     const T wp0 = vsel<T>(R[7] > R[5], T(1), T(-1)) * vsel<T>(t0 > T(0), sqrt(t0), T(0));
@@ -1172,7 +1176,7 @@ IKG_HD inline void pose_error(const T* Rh, const T* th, const T* RT, const T* tT
 // and V(w)^-1 commutes with the rotation, so log6(Rw, d) = blockdiag(Rh, Rh)
 // log6(Rm, pm): the reference's LOCAL error rotated into the frame's axes (same
 // norm, same minimum-norm step).
-template <typename T>
+template <typename T, bool COLD = false>
 IKG_HD inline void pose_error_aligned(const T* Rh, const T* th, const T* RT, const T* tT, T* e,
                                       ThetaTrack<T>* tk = nullptr, bool resync = true) {
   T Rw[9], d[3];
@@ -1183,7 +1187,7 @@ IKG_HD inline void pose_error_aligned(const T* Rh, const T* th, const T* RT, con
     e[0] = d[0]; e[1] = d[1]; e[2] = d[2];
     e[3] = T(0.5) * (Rw[7] - Rw[5]); e[4] = T(0.5) * (Rw[2] - Rw[6]); e[5] = T(0.5) * (Rw[3] - Rw[1]);
   } else {
-    log6_iter(Rw, d, e, tk, resync);
+    log6_iter<T, COLD>(Rw, d, e, tk, resync);
   }
 }
 
@@ -1422,7 +1426,7 @@ IKG_HD inline void trig_med_f1(const KModel<typename LaneT<T>::E>* __restrict__ 
 // none); the medium-range rule inline costs the broadcast kernel 4% fp64 /
 // 3.5% fp32 at C2, and the out-of-line form with it 21 register copies per
 // update (profiles/r04/trig/).
-template <typename T, bool MED = false>
+template <typename T, bool MED = false, bool COLD = false>
 IKG_HD inline void trig_advance_f1(const KModel<typename LaneT<T>::E>* __restrict__ m, int arm, T qc, const T* qa,
                                    const T* q_old, bool resync, T* sn, T* cs) {
   T dj[7], d[7];
@@ -1444,7 +1448,7 @@ IKG_HD inline void trig_advance_f1(const KModel<typename LaneT<T>::E>* __restric
     // common path then needs no register copies to merge the two
 #pragma unroll
     for (int j = 0; j < 7; ++j) Trig<T>::step(d[j], sn[j], cs[j]);
-    if (wave_any<T>(big)) {
+    if (IKG_RARELY(COLD, wave_any<T>(big))) {
       T se[7], ce[7];
       trig_exact_f1(m, arm, qc, qa, se, ce);
 #pragma unroll
@@ -1698,7 +1702,7 @@ IKG_HD inline void fk_f1(const KModel<typename LaneT<T>::E>* __restrict__ m, int
 // into frame 1 = chest Rz(q_root) at root_t, then arm joint 0 at p_0 with
 // Rz(q_0) (trig slots as trig_exact_f1), then log6 in the frame's axes;
 // st.e and the return value |e|^2.
-template <typename T, class SP>
+template <typename T, class SP, bool COLD = false>
 IKG_HD inline T pose_error_f1(const KModel<typename LaneT<T>::E>* __restrict__ m, int arm, const T* sn, const T* cs,
                               const T* RT, const T* tT, ArmStateF1<T>& st, const T* R, ThetaTrack<T>* tk,
                               bool resync) {
@@ -1716,18 +1720,18 @@ IKG_HD inline T pose_error_f1(const KModel<typename LaneT<T>::E>* __restrict__ m
   tT1[0] = cf * d0 + sf * d1 - st.k[0];
   tT1[1] = cf * d1 - sf * d0 - st.k[1];
   tT1[2] = tT[2] - m->root_t[2] - p0z;
-  pose_error_aligned(R, st.h, RT1, tT1, st.e, tk, resync);
+  pose_error_aligned<T, COLD>(R, st.h, RT1, tT1, st.e, tk, resync);
   const T* e = st.e;
   return e[0] * e[0] + e[1] * e[1] + e[2] * e[2] + e[3] * e[3] + e[4] * e[4] + e[5] * e[5];
 }
 
 // FK + pose error in frame 1 (inverse_geometry.py:58-67); returns |e|^2.
-template <typename T, class SP>
+template <typename T, class SP, bool COLD = false>
 IKG_HD inline T arm_fk_error_f1(const KModel<typename LaneT<T>::E>* __restrict__ m, int arm, const T* sn, const T* cs,
                                 const T* RT, const T* tT, ArmStateF1<T>& st, ThetaTrack<T>* tk, bool resync) {
   T R[9];
   fk_f1<T, SP>(m, arm, sn, cs, st, R);
-  return pose_error_f1<T, SP>(m, arm, sn, cs, RT, tT, st, R, tk, resync);
+  return pose_error_f1<T, SP, COLD>(m, arm, sn, cs, RT, tT, st, R, tk, resync);
 }
 
 // u = J_a^-1 e_a, v = J_a^-1 c_a in closed form (see above); alpha = u.v,

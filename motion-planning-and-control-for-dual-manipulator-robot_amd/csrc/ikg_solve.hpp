@@ -250,6 +250,37 @@ __device__ __forceinline__ void ck_put(typename LaneT<T>::E* c, int arm, int off
   }
 }
 
+// Where a retired problem's outputs go (the record-free frame-1 pair loop,
+// kScalarRetire below): this lane's pair's rows.
+template <typename E>
+struct PassOut {
+  const E* qrow;  // its q0 row (passive joints)
+  E* qo;          // its q_out row
+  uint8_t* conv;  // null: not wanted
+  int32_t* iters;
+  E* err;
+};
+
+// The record-free frame-1 pair loop retires lanes with scalars (DESIGN.md
+// §3a.8).  A per-lane `break` costs every update its bookkeeping: exec-mask
+// chains on three mask pairs, two saveexec + branch pairs, the count moved
+// through a VGPR.  Instead a pair whose errors pass writes its outputs at that
+// update, in a branch the whole wave skips unless a lane passes for the first
+// time (once per problem), and goes on iterating; its later iterates are never
+// stored.  "Done" is one 64-bit scalar mask and the loop leaves on scalar
+// tests.  IKG_SCALAR_RETIRE=0: the per-lane break, for timing A/Bs.
+#ifndef IKG_SCALAR_RETIRE
+#define IKG_SCALAR_RETIRE 1
+#endif
+// The same loop lays its rare wave-uniform branches (the exact acos, the near-pi axis, the
+// exact trig) off the common path (ikg_device.hpp IKG_RARELY).  IKG_COLD_PATHS=0: in line.
+#ifndef IKG_COLD_PATHS
+#define IKG_COLD_PATHS 1
+#endif
+// the instantiations that take it: record-free, frame-1 (lambda = 0), pair layout
+template <typename T, bool DAMPED, class SP, int REC>
+constexpr bool kScalarRetire = IKG_SCALAR_RETIRE && IKG_UNIFORM && !REC && kFrame1<SP> && !DAMPED && !is_packed<T>;
+
 // REC = 1: from the first passing iterate on, the window checkpoints go into
 // this problem's fixed slots (ikg_capi.hip sizes the launches so the slots fit
 // the record budget: no shared state, so a problem's checkpoints and answer do
@@ -266,13 +297,23 @@ template <typename T, bool DAMPED, class SP, bool MED = false, int REC = 0>
 __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict__ m,
                                   const KParams<typename LaneT<T>::E>& prm, int arm, const T* RT, const T* tT, T& qc,
                                   T* qa, int& it_out, bool& conv_out, T& nrm_out, T& other_out,
-                                  const RecOut<typename LaneT<T>::E>* ro = nullptr) {
+                                  const RecOut<typename LaneT<T>::E>* ro = nullptr,
+                                  const PassOut<typename LaneT<T>::E>* po = nullptr) {
   int k0 = -1;  // REC: the first iterate whose errors pass
   using E = typename LaneT<T>::E;
   E* recp = REC ? ro->rec : nullptr;  // this problem's records
   static_assert(!(DAMPED && is_packed<T>), "the packed layout implements lambda = 0 only");
   constexpr bool F1 = kFrame1<SP> && !DAMPED;  // frame-1 path, its own trig slots
   static_assert(!REC || F1, "records: the frame-1 loop only");
+  // lanes retire through the scalar done mask (po: where their outputs go)
+  constexpr bool RETIRE = kScalarRetire<T, DAMPED, SP, REC>;
+  constexpr bool COLD = RETIRE && IKG_COLD_PATHS;
+  uint64_t done = 0, live = 0;  // RETIRE: the lanes whose outputs are written / that entered the loop
+  if constexpr (RETIRE) live = __builtin_amdgcn_ballot_w64(true);
+  int stop_at = prm.max_iters;  // RETIRE: the count at which the loop leaves
+  // RETIRE: it % kResync, formed once per update for the trig advance and carried to the next
+  // update's FK (a bool carried round the loop becomes a lane mask, so the count is carried)
+  int rs_phase = 0;
   T sn[7], cs[7];
   int it = 0;
   ThetaTrack<T> tk{};
@@ -315,6 +356,11 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
 #pragma unroll
   for (int i = 0; i < 8; ++i) pad[i] = qc + T(i);
 #endif
+#ifdef IKG_PAD_SALU
+  // timing experiment: IKG_PAD_SALU scalar ALU instructions per iteration (add, xor), one chain
+  // in one register: the kernel is at its scalar register limit
+  uint32_t spad = __builtin_amdgcn_readfirstlane(prm.max_iters);
+#endif
 #ifdef IKG_STAGE_CLOCK
   unsigned long long sc_acc[5] = {0, 0, 0, 0, 0}, sc_t0 = 0, sc_t1 = 0, sc_r0, sc_r1, sc_l0, sc_l1;
   IKG_RSTAMP(sc_r0);
@@ -327,6 +373,22 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
 #pragma unroll
       for (int i = 0; i < 8; ++i) pad[i] = pad[i] * T(0.999999) + T(1e-7);
 #endif
+#ifdef IKG_PAD_SALU
+#pragma unroll
+    for (int k = 0; k < IKG_PAD_SALU; ++k) spad = (k & 1) ? spad ^ (uint32_t)it : spad + 0x9e3779b9u;
+#endif
+#ifdef IKG_PAD_BRN  // IKG_PAD_BRN wave-uniform branches per iteration, never taken (exec is not 0)
+#pragma unroll
+    for (int k = 0; k < IKG_PAD_BRN; ++k) asm volatile("s_cbranch_execz .Likg_brn%=\n.Likg_brn%=:" ::);
+#endif
+#ifdef IKG_PAD_BRT  // IKG_PAD_BRT wave-uniform branches per iteration, always taken, each over 64 bytes of code
+#pragma unroll
+    for (int k = 0; k < IKG_PAD_BRT; ++k)
+      asm volatile(
+          "s_cbranch_execnz .Likg_brt%=\n"
+          ".rept 16\n\ts_nop 0\n.endr\n"
+          ".Likg_brt%=:" ::);
+#endif
 #if IKG_UNIFORM
     // every live lane of the wave has run the same number of updates, so the
     // count (and the resync / max_iters tests on it) is wave-uniform: scalar
@@ -337,7 +399,7 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
     ThetaTrack<T>* tkp = (IKG_THETA_TRACK && is_f64<T>) ? &tk : nullptr;
     // the record-writing kernels resync at every window start (kRsRec)
     constexpr int kRs = REC ? kRsRec<T> : Trig<T>::kResync;
-    const bool resync = (it % kRs) == 0;
+    const bool resync = RETIRE ? rs_phase == 0 : (it % kRs) == 0;
     // the step is formed before the stop test (discarded when the loop ends)
     // so the test's exchange/compare overlaps the solve instead of heading it
     T dq[6], alpha, beta, s;
@@ -345,14 +407,14 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
       ArmStateF1<T> st;
 #ifdef IKG_STAGE_CLOCK
       IKG_STAMP(sc_t0);
-      x = arm_fk_error_f1<T, SP>(m, arm, sn, cs, RT, tT, st, tkp, resync);
+      x = arm_fk_error_f1<T, SP, COLD>(m, arm, sn, cs, RT, tT, st, tkp, resync);
       IKG_STAMP(sc_t1);
       sc_acc[0] += sc_t1 - sc_t0;
       pinv_step_f1<T, SP, PairX, !REC>(m, arm, st, sn, cs, dq, s);
       IKG_STAMP(sc_t0);
       sc_acc[1] += sc_t0 - sc_t1;
 #else
-      x = arm_fk_error_f1<T, SP>(m, arm, sn, cs, RT, tT, st, tkp, resync);
+      x = arm_fk_error_f1<T, SP, COLD>(m, arm, sn, cs, RT, tT, st, tkp, resync);
       pinv_step_f1<T, SP, PairX, !REC>(m, arm, st, sn, cs, dq, s);
 #endif
     } else {
@@ -449,6 +511,28 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
         }
       }
       if (ended) break;
+    } else if constexpr (RETIRE) {
+      // the loop's one exit.  it == max_iters: loop exhausted, the reference never tests this
+      // iterate; or every lane's outputs were written at the update before (stop_at)
+      if (__builtin_expect(it >= stop_at, 0)) break;
+      // the pairs passing for the first time (both lanes of a pair pass together); one ballot
+      // per compare: the ballot of their conjunction goes through a select and a compare
+      const uint64_t fresh =
+          __builtin_amdgcn_ballot_w64(x < prm.eps2) & __builtin_amdgcn_ballot_w64(xo < prm.eps2) & ~done;
+      if (__builtin_expect(fresh != 0, 0)) {  // wave-uniform; taken once per problem
+        if ((fresh >> (threadIdx.x & 63)) & 1) {
+          store_q(m, arm, po->qrow, it, qc, qa, po->qo);
+          if (arm == 0) {
+            if (po->conv) *po->conv = 1;
+            if (po->iters) *po->iters = it;
+          }
+          if (po->err) po->err[arm] = sqrt(x);
+        }
+        done |= fresh;
+        // a second exit here costs every update a flag that tells the exits apart: leave at
+        // the next update's test instead (one update more, once per wave, nothing stored)
+        if (done == live) stop_at = it;
+      }
     } else {
       if (it >= prm.max_iters) break;  // loop exhausted: the reference never tests this iterate
       if (both_below(x, xo, prm.eps2)) {  // |e_L| < eps and |e_R| < eps (:70)
@@ -479,7 +563,10 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
     sc_acc[3] += sc_t0 - sc_t1;
 #endif
     if constexpr (F1) {
-      trig_advance_f1<T, MED>(m, arm, qc, qa, q_old, (it % (REC ? kRsRec<T> : Trig<T>::kResync)) == 0, sn, cs);
+      // RETIRE: one resync predicate per update, this advance's is the next update's
+      if constexpr (RETIRE) rs_phase = it % Trig<T>::kResync;
+      const bool rs = RETIRE ? rs_phase == 0 : (it % (REC ? kRsRec<T> : Trig<T>::kResync)) == 0;
+      trig_advance_f1<T, MED, COLD>(m, arm, qc, qa, q_old, rs, sn, cs);
 #ifdef IKG_STAGE_CLOCK
       IKG_STAMP(sc_t1);
       sc_acc[4] += sc_t1 - sc_t0;
@@ -504,6 +591,9 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
 #pragma unroll
   for (int i = 0; i < 8; ++i) ps += pad[i];
   if (any_of(ps == T(-12345.678))) it = -1;  // never true; keeps the padding live
+#endif
+#ifdef IKG_PAD_SALU
+  if (spad == 0x7ffffff1u) it = -1;  // keeps the padding live
 #endif
   if constexpr (REC) {
     if constexpr (REC == 2) {  // records only: the scan writes the outputs
@@ -549,6 +639,7 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
   nrm_out = sqrt(x);
   other_out = sqrt(xo);
   conv_out = conv;
+  if constexpr (RETIRE) return (done >> (threadIdx.x & 63)) & 1;  // its outputs were written when it passed
   return REC && k0 >= 0;  // the outputs came from the records
 }
 
@@ -638,6 +729,10 @@ __device__ inline void pair_batch_body(const KModel<T>* __restrict__ m, const KP
                  conv_out + p, iters_out + p, err_out + p * 2, rl, ra.ck + p * ck_per_problem<T>(prm.max_iters)};
     if (arm == 0) ra.nrec[p] = 0;
     if (solve_pair<T, DAMPED, SP, MED, 1>(m, prm, arm, RT, tT, qc, qa, it, conv, nrm, other, &ro)) return;
+  } else if constexpr (kScalarRetire<T, DAMPED, SP, REC>) {  // a pair that passes writes its outputs in the loop
+    const PassOut<T> po{qrow, q_out + p * m->nq, conv_out ? conv_out + p : nullptr,
+                        iters_out ? iters_out + p : nullptr, err_out ? err_out + p * 2 : nullptr};
+    if (solve_pair<T, DAMPED, SP, MED>(m, prm, arm, RT, tT, qc, qa, it, conv, nrm, other, nullptr, &po)) return;
   } else {
     solve_pair<T, DAMPED, SP, MED>(m, prm, arm, RT, tT, qc, qa, it, conv, nrm, other);
   }
