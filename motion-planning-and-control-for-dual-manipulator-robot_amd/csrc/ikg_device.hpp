@@ -759,14 +759,53 @@ IKG_HD inline T atan2_upper(T y, T x) {
   return vsel<T>(x < T(0), T(3.14159274f) - r, r);
 }
 
-template <typename T, bool COLD = false>
+// a + b and a - b that never take a product into a fused multiply-add
+template <typename T>
+IKG_HD inline T add_plain(T a, T b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+template <typename T>
+IKG_HD inline T sub_plain(T a, T b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+#ifdef __HIP_DEVICE_COMPILE__
+constexpr bool kDeviceCode = true;
+#else
+constexpr bool kDeviceCode = false;
+#endif
+
+// a * b + c with one rounding, whatever the contraction mode (float, double)
+template <typename T>
+IKG_HD inline T fma1(T a, T b, T c) {
+  if constexpr (is_f64<T>)
+    return __builtin_fma(a, b, c);
+  else if constexpr (is_packed<T>)
+    return a * b + c;  // not used by the packed layout
+  else
+    return __builtin_fmaf(a, b, c);
+}
+
+// ROW3 (pose_error_f1's z-aligned form): R's third row is the hand rotation's third column
+// itself, not a sum of products.  Where that column's entry is a bare product the compiler
+// would contract it into the sums below that read it (one rounding less than the general form,
+// where the entry comes out of a multiplication by RT1[8]: other bits), so those sums are
+// formed with contraction off (add_plain, sub_plain).  Their other operands are sums of products, which never contract
+// further, so nothing else changes.
+template <typename T, bool COLD = false, bool ROW3 = false>
 IKG_HD inline void log6_iter(const T* R, const T* p, T* e, ThetaTrack<T>* tk = nullptr, bool resync = true) {
   using M = typename LaneT<T>::M;
   const T pi = T(Prec<T>::kPi);
-  const T tr = R[0] + R[4] + R[8];
-  const T sx = R[7] - R[5], sy = R[2] - R[6], sz = R[3] - R[1];
+  const T tr = ROW3 ? add_plain(add_plain(R[0], R[4]), R[8]) : R[0] + R[4] + R[8];
+  const T sx = ROW3 ? sub_plain(R[7], R[5]) : R[7] - R[5], sy = ROW3 ? sub_plain(R[2], R[6]) : R[2] - R[6],
+          sz = ROW3 ? sub_plain(R[3], R[1]) : R[3] - R[1];
   const T ct = (tr - T(1)) * T(0.5);
-  const T st = fsqrt_unit(sx * sx + sy * sy + sz * sz) * T(0.5);
+  // ROW3: which of the two first squares is rounded before the sum is the compiler's choice, and
+  // with sx and sy plain differences it chooses the other one: written out as the general form
+  // compiles on the device (sy * sy rounded, then sx, then sz fused)
+  const T st = fsqrt_unit(ROW3 && kDeviceCode ? fma1(sz, sz, fma1(sx, sx, sy * sy)) : sx * sx + sy * sy + sz * sz) *
+               T(0.5);
   T theta = T(0);
   if constexpr (is_f64<T>) {
     bool exact = true;
@@ -823,7 +862,7 @@ IKG_HD inline void log6_iter(const T* R, const T* p, T* e, ThetaTrack<T>* tk = n
   const M near_pi = theta >= pi - T(1e-2);
   if (IKG_RARELY(COLD, wave_any<T>(any_of(near_pi)))) {  // near pi (rare): the axis from the diagonal
     const T beta = fdiv<T>(t2, T(1) - ct);
-    const T t0 = (R[0] - ct) * beta, t1 = (R[4] - ct) * beta, tt = (R[8] - ct) * beta;
+    const T t0 = (R[0] - ct) * beta, t1 = (R[4] - ct) * beta, tt = (ROW3 ? sub_plain(R[8], ct) : R[8] - ct) * beta;
     const T wp0 = vsel<T>(R[7] > R[5], T(1), T(-1)) * vsel<T>(t0 > T(0), sqrt(t0), T(0));
     const T wp1 = vsel<T>(R[2] > R[6], T(1), T(-1)) * vsel<T>(t1 > T(0), sqrt(t1), T(0));
     const T wp2 = vsel<T>(R[3] > R[1], T(1), T(-1)) * vsel<T>(tt > T(0), sqrt(tt), T(0));
@@ -1176,7 +1215,7 @@ IKG_HD inline void pose_error(const T* Rh, const T* th, const T* RT, const T* tT
 // and V(w)^-1 commutes with the rotation, so log6(Rw, d) = blockdiag(Rh, Rh)
 // log6(Rm, pm): the reference's LOCAL error rotated into the frame's axes (same
 // norm, same minimum-norm step).
-template <typename T, bool COLD = false>
+template <typename T, bool COLD = false, bool ROW3 = false>
 IKG_HD inline void pose_error_aligned(const T* Rh, const T* th, const T* RT, const T* tT, T* e,
                                       ThetaTrack<T>* tk = nullptr, bool resync = true) {
   T Rw[9], d[3];
@@ -1187,7 +1226,7 @@ IKG_HD inline void pose_error_aligned(const T* Rh, const T* th, const T* RT, con
     e[0] = d[0]; e[1] = d[1]; e[2] = d[2];
     e[3] = T(0.5) * (Rw[7] - Rw[5]); e[4] = T(0.5) * (Rw[2] - Rw[6]); e[5] = T(0.5) * (Rw[3] - Rw[1]);
   } else {
-    log6_iter<T, COLD>(Rw, d, e, tk, resync);
+    log6_iter<T, COLD, ROW3>(Rw, d, e, tk, resync);
   }
 }
 
@@ -1702,7 +1741,12 @@ IKG_HD inline void fk_f1(const KModel<typename LaneT<T>::E>* __restrict__ m, int
 // into frame 1 = chest Rz(q_root) at root_t, then arm joint 0 at p_0 with
 // Rz(q_0) (trig slots as trig_exact_f1), then log6 in the frame's axes;
 // st.e and the return value |e|^2.
-template <typename T, class SP, bool COLD = false>
+// ZT: the target is a rotation about z (RT[2], [5], [6], [7] == 0, RT[8] == 1,
+// z_aligned below), so RT1 keeps those five entries and they are written as
+// literals: the products of Rw = RT1 Rh^T that multiply them fold away.  The
+// surviving sums keep their shape, an exact 0 x term adds nothing and an exact
+// 1 x is x, so the error has the bits of the general form.
+template <typename T, class SP, bool COLD = false, bool ZT = false>
 IKG_HD inline T pose_error_f1(const KModel<typename LaneT<T>::E>* __restrict__ m, int arm, const T* sn, const T* cs,
                               const T* RT, const T* tT, ArmStateF1<T>& st, const T* R, ThetaTrack<T>* tk,
                               bool resync) {
@@ -1716,22 +1760,26 @@ IKG_HD inline T pose_error_f1(const KModel<typename LaneT<T>::E>* __restrict__ m
     RT1[3 + c] = cf * RT[3 + c] - sf * RT[c];
     RT1[6 + c] = RT[6 + c];
   }
+  if constexpr (ZT) {
+    RT1[2] = RT1[5] = RT1[6] = RT1[7] = T(0);
+    RT1[8] = T(1);
+  }
   const T d0 = tT[0] - m->root_t[0], d1 = tT[1] - m->root_t[1];
   tT1[0] = cf * d0 + sf * d1 - st.k[0];
   tT1[1] = cf * d1 - sf * d0 - st.k[1];
   tT1[2] = tT[2] - m->root_t[2] - p0z;
-  pose_error_aligned<T, COLD>(R, st.h, RT1, tT1, st.e, tk, resync);
+  pose_error_aligned<T, COLD, ZT>(R, st.h, RT1, tT1, st.e, tk, resync);
   const T* e = st.e;
   return e[0] * e[0] + e[1] * e[1] + e[2] * e[2] + e[3] * e[3] + e[4] * e[4] + e[5] * e[5];
 }
 
 // FK + pose error in frame 1 (inverse_geometry.py:58-67); returns |e|^2.
-template <typename T, class SP, bool COLD = false>
+template <typename T, class SP, bool COLD = false, bool ZT = false>
 IKG_HD inline T arm_fk_error_f1(const KModel<typename LaneT<T>::E>* __restrict__ m, int arm, const T* sn, const T* cs,
                                 const T* RT, const T* tT, ArmStateF1<T>& st, ThetaTrack<T>* tk, bool resync) {
   T R[9];
   fk_f1<T, SP>(m, arm, sn, cs, st, R);
-  return pose_error_f1<T, SP, COLD>(m, arm, sn, cs, RT, tT, st, R, tk, resync);
+  return pose_error_f1<T, SP, COLD, ZT>(m, arm, sn, cs, RT, tT, st, R, tk, resync);
 }
 
 // u = J_a^-1 e_a, v = J_a^-1 c_a in closed form (see above); alpha = u.v,
@@ -2394,6 +2442,13 @@ IKG_HD inline void hook_target(const KModel<T>* __restrict__ m, int arm, const T
   matvec3(CR, Ht, d);
 #pragma unroll
   for (int i = 0; i < 3; ++i) tT[i] = Ct[i] + d[i];
+}
+
+// A hook target that is a rotation about z: the five entries the ZT form of
+// pose_error_f1 writes as literals, compared by value (-0.0 counts as 0).
+template <typename T>
+IKG_HD inline bool z_aligned(const T* RT) {
+  return RT[2] == T(0) && RT[5] == T(0) && RT[6] == T(0) && RT[7] == T(0) && RT[8] == T(1);
 }
 
 // Both arms' hook targets in one packed lane (x = left, y = right).

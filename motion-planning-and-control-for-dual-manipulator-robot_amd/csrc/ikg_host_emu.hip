@@ -25,6 +25,9 @@ thread_local long long svd_count = 0;  // of those, with an arm that pins the ch
 // updates whose two arm lanes computed different chest steps (must stay 0:
 // each lane carries the shared chest joint); ikg_emu_solve returns -3 then
 thread_local long long chest_mismatch = 0;
+// ikg_emu_force_general(1): the general pose error for z-aligned targets too (the loop a wave
+// runs when it also holds another target); tests/test_zaligned.py compares the two
+thread_local bool force_general = false;
 
 // collide_wave's stages run serially (same functions, same order per lane).
 template <typename T>
@@ -60,6 +63,8 @@ void emu_one(const ikg::KModel<T>& m, const ikg::KParams<T>& prm, bool damped, c
     qc[arm] = qrow[m.root_q];
     for (int k = 0; k < kArmDof; ++k) qa[arm][k] = qrow[m.arm_q[arm][k]];
   }
+  // the kernel's choice (pair_batch_body) for a wave that holds this problem alone
+  const bool zt = !force_general && z_aligned(RT[0]) && z_aligned(RT[1]);
   int it = 0;
   bool conv = false;
   T nrm[2];
@@ -80,7 +85,8 @@ void emu_one(const ikg::KModel<T>& m, const ikg::KParams<T>& prm, bool damped, c
     for (int arm = 0; arm < 2; ++arm) {
       if constexpr (kFrame1<SP>) {
         if (f1) {
-          nrm[arm] = arm_fk_error_f1<T, SP>(&m, arm, sn[arm], cs[arm], RT[arm], tT[arm], s1[arm], tkp[arm], resync);
+          nrm[arm] = (zt ? arm_fk_error_f1<T, SP, false, true> : arm_fk_error_f1<T, SP, false, false>)(
+              &m, arm, sn[arm], cs[arm], RT[arm], tT[arm], s1[arm], tkp[arm], resync);
           continue;
         }
       }
@@ -256,6 +262,30 @@ extern "C" int ikg_emu_solve(const ikg_model_desc* d, int dtype, const void* tar
   else
     emu<float>(d, targets, q0, q0_stride, B, p, q_out, conv, iters, err, trace, trace_len, cd);
   return chest_mismatch ? -3 : 0;
+}
+
+// The general pose-error loop for every target (on != 0), or the kernel's choice (0).
+extern "C" void ikg_emu_force_general(int on) { force_general = on != 0; }
+
+// The kernel's z-aligned test (z_aligned on hook_target's rotation) of n targets
+// [n][12]: out[2 i + arm] = 1 where arm's hook target of target i passes.
+template <typename T>
+void emu_z_aligned(const ikg_model_desc* d, const void* targets, int64_t n, uint8_t* out) {
+  static thread_local ikg::KModel<T> m;
+  ikg::build_kmodel<T>(*d, m);
+  for (int64_t i = 0; i < n; ++i)
+    for (int arm = 0; arm < 2; ++arm) {
+      T RT[9], tT[3];
+      ikg::hook_target(&m, arm, (const T*)targets + 12 * i, RT, tT);
+      out[2 * i + arm] = ikg::z_aligned(RT) ? 1 : 0;
+    }
+}
+extern "C" int ikg_emu_z_aligned(const ikg_model_desc* d, int dtype, const void* targets, int64_t n, uint8_t* out) {
+  if (dtype == IKG_F64)
+    emu_z_aligned<double>(d, targets, n, out);
+  else
+    emu_z_aligned<float>(d, targets, n, out);
+  return 0;
 }
 
 // Which tables and specialisation a model gets (tests/test_robot_family.py):

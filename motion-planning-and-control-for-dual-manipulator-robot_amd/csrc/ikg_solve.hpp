@@ -277,6 +277,11 @@ struct PassOut {
 #ifndef IKG_COLD_PATHS
 #define IKG_COLD_PATHS 1
 #endif
+// The same loop has a second copy for waves whose targets are all rotations about z
+// (pair_batch_body).  IKG_ZT=0: the general loop for every wave.
+#ifndef IKG_ZT
+#define IKG_ZT 1
+#endif
 // the instantiations that take it: record-free, frame-1 (lambda = 0), pair layout
 template <typename T, bool DAMPED, class SP, int REC>
 constexpr bool kScalarRetire = IKG_SCALAR_RETIRE && IKG_UNIFORM && !REC && kFrame1<SP> && !DAMPED && !is_packed<T>;
@@ -293,7 +298,9 @@ constexpr bool kScalarRetire = IKG_SCALAR_RETIRE && IKG_UNIFORM && !REC && kFram
 // of q (fp64 ~1e-16), not bit for bit.  One instantiation serving both was
 // bit-exact but made the batch kernel 33% slower (1,036 -> 1,382 us at C2:
 // register allocation around the resume branch), profiles/r06/records/.
-template <typename T, bool DAMPED, class SP, bool MED = false, int REC = 0>
+// ZT (record-free frame-1 pair loop only): every target of the wave is a rotation about z, the
+// pose error drops the terms that multiply its exact zeros and one (pose_error_f1; same bits).
+template <typename T, bool DAMPED, class SP, bool MED = false, int REC = 0, bool ZT = false>
 __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict__ m,
                                   const KParams<typename LaneT<T>::E>& prm, int arm, const T* RT, const T* tT, T& qc,
                                   T* qa, int& it_out, bool& conv_out, T& nrm_out, T& other_out,
@@ -308,6 +315,7 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
   // lanes retire through the scalar done mask (po: where their outputs go)
   constexpr bool RETIRE = kScalarRetire<T, DAMPED, SP, REC>;
   constexpr bool COLD = RETIRE && IKG_COLD_PATHS;
+  static_assert(!ZT || RETIRE, "z-aligned targets: the record-free frame-1 pair loop only");
   uint64_t done = 0, live = 0;  // RETIRE: the lanes whose outputs are written / that entered the loop
   if constexpr (RETIRE) live = __builtin_amdgcn_ballot_w64(true);
   int stop_at = prm.max_iters;  // RETIRE: the count at which the loop leaves
@@ -407,14 +415,14 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
       ArmStateF1<T> st;
 #ifdef IKG_STAGE_CLOCK
       IKG_STAMP(sc_t0);
-      x = arm_fk_error_f1<T, SP, COLD>(m, arm, sn, cs, RT, tT, st, tkp, resync);
+      x = arm_fk_error_f1<T, SP, COLD, ZT>(m, arm, sn, cs, RT, tT, st, tkp, resync);
       IKG_STAMP(sc_t1);
       sc_acc[0] += sc_t1 - sc_t0;
       pinv_step_f1<T, SP, PairX, !REC>(m, arm, st, sn, cs, dq, s);
       IKG_STAMP(sc_t0);
       sc_acc[1] += sc_t0 - sc_t1;
 #else
-      x = arm_fk_error_f1<T, SP, COLD>(m, arm, sn, cs, RT, tT, st, tkp, resync);
+      x = arm_fk_error_f1<T, SP, COLD, ZT>(m, arm, sn, cs, RT, tT, st, tkp, resync);
       pinv_step_f1<T, SP, PairX, !REC>(m, arm, st, sn, cs, dq, s);
 #endif
     } else {
@@ -732,7 +740,25 @@ __device__ inline void pair_batch_body(const KModel<T>* __restrict__ m, const KP
   } else if constexpr (kScalarRetire<T, DAMPED, SP, REC>) {  // a pair that passes writes its outputs in the loop
     const PassOut<T> po{qrow, q_out + p * m->nq, conv_out ? conv_out + p : nullptr,
                         iters_out ? iters_out + p : nullptr, err_out ? err_out + p * 2 : nullptr};
+#if IKG_ZT
+    // every lane still here holds a z-aligned target: the wave runs the ZT loop (one choice per
+    // launch; the lanes that left above are in neither ballot).  Both loops give an aligned
+    // problem the same bits, so its answer does not depend on which targets share its wave.
+    // The two markers differ on purpose: without them the compiler merges the loops' identical
+    // preheaders (exact trig, hoisted model tables) into one block whose values then live across
+    // both loops, and the general loop spills on its common path (496 instructions for 477,
+    // DESIGN.md §3a.9); with a preheader each, either loop is allocated as if it were alone.
+    if (__builtin_amdgcn_ballot_w64(z_aligned(RT)) == __builtin_amdgcn_ballot_w64(true)) {
+      asm volatile("; z-aligned loop" : "+v"(qc));
+      if (solve_pair<T, DAMPED, SP, MED, 0, true>(m, prm, arm, RT, tT, qc, qa, it, conv, nrm, other, nullptr, &po))
+        return;
+    } else {
+      asm volatile("; general loop" : "+v"(qc));
+      if (solve_pair<T, DAMPED, SP, MED>(m, prm, arm, RT, tT, qc, qa, it, conv, nrm, other, nullptr, &po)) return;
+    }
+#else
     if (solve_pair<T, DAMPED, SP, MED>(m, prm, arm, RT, tT, qc, qa, it, conv, nrm, other, nullptr, &po)) return;
+#endif
   } else {
     solve_pair<T, DAMPED, SP, MED>(m, prm, arm, RT, tT, qc, qa, it, conv, nrm, other);
   }

@@ -13,6 +13,8 @@ for c in ${CONFIGS:-c2_f64 c2_f64_forced c3_f32 rand_f64}; do
   case $c in
     c2_f64) run $c 12 4096 f64 ABL_EPS=1e-3 ;;
     c2_f64_forced) run $c 8 4096 f64 ;;                      # every problem runs 1,000 updates
+    c2_f64_yaw) run $c 12 4096 f64 ABL_EPS=1e-3 ABL_YAW=0.785 ;;
+    c2_f64_tilt) run $c 12 4096 f64 ABL_EPS=1e-3 ABL_TILT=0.05 ;;  # small seeded roll + pitch: no wave takes the z-aligned loop
     c2_f32) run $c 10 4096 f32 ABL_EPS=1e-3 ;;
     c3_f32) run $c 8 65536 f32 ABL_EPS=1e-3 ;;
     c4s_f64) run $c 6 131072 f64 ABL_EPS=1e-3 ;;

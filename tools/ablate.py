@@ -22,7 +22,17 @@ libs = [f for pat in pattern.split() for f in sorted(glob.glob(pat))]
 dev = torch.device("cuda", 0)
 tdt = torch.float64 if dtype == "f64" else torch.float32
 code = 0 if dtype == "f64" else 1
-tg = torch.tensor(uniform_targets(B, seed=0), dtype=tdt, device=dev)
+tgn = uniform_targets(B, seed=0, yaw=float(os.environ.get("ABL_YAW", "0")))
+TILT = float(os.environ.get("ABL_TILT", "0"))
+if TILT > 0:  # general (not z-aligned) targets: a seeded roll and pitch ~ U[-TILT, TILT] rad on every cube
+    rng = np.random.default_rng(2000)
+    for i, j in ((1, 2), (2, 0)):  # Rx(roll), then Ry(pitch), applied on the right
+        a = rng.uniform(-TILT, TILT, B)
+        G = np.tile(np.eye(3), (B, 1, 1))
+        G[:, i, i] = G[:, j, j] = np.cos(a)
+        G[:, i, j], G[:, j, i] = -np.sin(a), np.sin(a)
+        tgn[:, :9] = (tgn[:, :9].reshape(B, 3, 3) @ G).reshape(B, 9)
+tg = torch.tensor(tgn, dtype=tdt, device=dev)
 if os.environ.get("ABL_RANDQ0"):  # multi-start-like problems: random seeds (workload.random_seeds)
     from ikgrasp.workload import random_seeds  # noqa: E402
     q0 = torch.tensor(random_seeds(load_nextage(), B, seed=1000), dtype=tdt, device=dev)
