@@ -511,6 +511,74 @@ int ikg_control_rollout(const ikg_model* model, int device, const void* q0, cons
                         const ikg_bezier* q_curve, const ikg_bezier* v_curve, const ikg_rollout_params* params,
                         const ikg_rollout_out* out, void* stream, uint32_t flags);
 
+/*
+ * ikg_control_rollout with one curve pair PER STATE: state p follows
+ * q_curves->points[p] and v_curves->points[p].  Everything else is the entry
+ * above tick for tick (clamping, torque law, plant, Euler step, records,
+ * 65,536-state chunks -- the curves chunk with their states -- and graph
+ * capture): the same kernels read each state's control points through a
+ * per-state stride (stride 0 = the shared pair of ikg_control_rollout), so B
+ * equal curves give the shared entry's result bit for bit.
+ *   points [B, n_points, nq]: device array, or host with IKG_FLAG_HOST_POINTERS
+ *   (then checked for finiteness); it is read during the ticks and must not
+ *   overlap an output.  n_points, the range and mult are common to all states
+ *   (n_points 2 .. 64, t_max > t_min); t0 NULL = the q curves' t_min.
+ */
+typedef struct ikg_bezier_set {
+  const void* points; /* [B, n_points, nq], device or host per flag */
+  int32_t n_points;
+  double t_min, t_max, mult;
+} ikg_bezier_set;
+int ikg_control_rollout_curves(const ikg_model* model, int device, const void* q0, const void* v0, const void* t0,
+                               int64_t B, const ikg_bezier_set* q_curves, const ikg_bezier_set* v_curves,
+                               const ikg_rollout_params* params, const ikg_rollout_out* out, void* stream,
+                               uint32_t flags);
+
+/*
+ * Batched Bezier trajectory fit: the reference's maketraj (control.py:63-197)
+ * for B paths in one launch (fp64).  The reference runs SLSQP over all
+ * (degree + 1) x dim control points under six equality constraints (end
+ * positions, zero end velocities and accelerations).  Those pin
+ *   P[0] = P[1] = P[2] = q0,   P[degree-2] = P[degree-1] = P[degree] = q1,
+ * and what is left is linear least squares in the degree - 5 free points, per
+ * joint: with X0 = linspace(q0, q1, degree + 1), the reference's initial guess,
+ *   min_delta | A_f (X0_f + delta) + c - Y |^2 + ridge |delta|^2,
+ *   A_f[k,i] = C(degree,i) u_k^i (1 - u_k)^(degree-i), i = 3 .. degree-3,
+ * c the pinned points' share, u_k = t_k / total_time with t = numpy's
+ * linspace(0, total_time, n) (t_k = k (total_time / (n - 1)), t_{n-1} = total_time).
+ * It is solved by a Householder factorisation of [A_f; sqrt(ridge) 1] (the normal
+ * equations lose the control points: cond(A_f) ~ 2e5 at degree 20).  With
+ * ridge = 0 and n >= degree - 3 this is the reference's problem and the result
+ * its exact minimiser; ridge > 0 picks, for shorter paths, the solution nearest
+ * X0 and damps the control polygon on noisy paths.
+ *   q0, q1 [B,dim]; path_points packed [offsets[B],dim], path p = rows
+ *   offsets[p] .. offsets[p+1]-1 (offsets [B+1], offsets[0] = 0; y_0 need not be q0).
+ *   points  [B,degree+1,dim]  P[0..2] = q0 and P[degree-2..degree] = q1 are copies
+ *   vpoints [B,degree,dim], apoints [B,degree-1,dim] (optional): the unscaled
+ *           derivative control points as Bezier.derivative forms them,
+ *           degree (P[i+1] - P[i]) and again; the 1 / total_time factors stay
+ *           with the caller (ikg_bezier.mult)
+ *   cost    [B]  sum_k |B(t_k) - y_k|^2 with the reference's Horner (result.fun)
+ *   status  [B]  0 = solved, 1 = the path's point count is out of range
+ * Limits: degree 6 .. 20, dim 1 .. IKG_MAX_NQ, 2 <= n <= 256 per path and
+ * n >= degree - 3 unless ridge > 0, total_time > 0, ridge >= 0.  All arrays,
+ * offsets included, are device arrays, or host arrays with
+ * IKG_FLAG_HOST_POINTERS; a host-pointer call checks every limit and the inputs'
+ * finiteness and returns IKG_EINVAL before any launch.  With device pointers the
+ * kernel refuses a path whose count is out of range: status 1, cost NaN, its
+ * points untouched, its neighbours unaffected.  B == 0 is a no-op.
+ * Stream-ordered, no scratch, capturable.
+ */
+typedef struct ikg_fit_params {
+  int32_t degree;    /* 20 (control.py:85) */
+  double ridge;      /* 0 */
+  double total_time; /* 1 */
+} ikg_fit_params;
+void ikg_fit_params_default(ikg_fit_params* p);
+int ikg_bezier_fit_batch(int device, const void* q0, const void* q1, const void* path_points, const int64_t* offsets,
+                         int64_t B, int32_t dim, const ikg_fit_params* params, void* points, void* vpoints,
+                         void* apoints, void* cost, int32_t* status, void* stream, uint32_t flags);
+
 /* Thread-local message of the last failure ("" if none). */
 const char* ikg_last_error(void);
 

@@ -17,6 +17,7 @@
 #include "ikg_jit.hpp"
 #include "ikg_solve.hpp"
 #include "ikg_launch.hpp"
+#include "ikg_fit.hpp"
 #include "ikg_model_build.hpp"
 #include "ikgrasp.h"
 
@@ -1236,8 +1237,29 @@ void append_curve(std::vector<double>& tab, const ikg_bezier& c, int dim) {
   tab.insert(tab.end(), bc, bc + c.n_points);
 }
 
+// [bc (n)] of a curve whose control points stay with the caller (one curve per state)
+void append_coeffs(std::vector<double>& tab, int n_points) {
+  double bc[ikg::kMaxBezier];
+  ikg::bezier_coeffs(n_points, bc);
+  tab.insert(tab.end(), bc, bc + n_points);
+}
+
+// A rollout's curve: one for all states (ikg_bezier, host control points) or one
+// per state (ikg_bezier_set, [B,n_points,nq] device or host per flag)
+struct CurveArg {
+  const double* shared;
+  const void* per_state;
+  int32_t n_points;
+  double t_min, t_max, mult;
+  explicit CurveArg(const ikg_bezier& c)
+      : shared(c.points), per_state(nullptr), n_points(c.n_points), t_min(c.t_min), t_max(c.t_max), mult(c.mult) {}
+  explicit CurveArg(const ikg_bezier_set& c)
+      : shared(nullptr), per_state(c.points), n_points(c.n_points), t_min(c.t_min), t_max(c.t_max), mult(c.mult) {}
+  ikg_bezier one() const { return ikg_bezier{shared, n_points, t_min, t_max, mult}; }
+};
+
 int control_rollout(ikg_model* model, int device, const void* q0, const void* v0, const void* t0, int64_t B,
-                    const ikg_bezier& bq, const ikg_bezier& bv, const ikg_rollout_params& params,
+                    const CurveArg& bq, const CurveArg& bv, const ikg_rollout_params& params,
                     const ikg_rollout_out& out, hipStream_t s, uint32_t flags) {
   using T = double;
   CtlTables t;
@@ -1252,10 +1274,20 @@ int control_rollout(ikg_model* model, int device, const void* q0, const void* v0
   const void* dv0 = st.in(v0, sizeof(T) * nq * B);
   const void* dt0 = st.in(t0, sizeof(T) * B);
   for (int i = 0; i < 6; ++i) o[i] = st.out(o[i], sizeof(T) * sz[i] * B);
+  const bool per_state = bq.per_state != nullptr;
+  const int64_t stride_q = per_state ? (int64_t)bq.n_points * nq : 0;
+  const int64_t stride_v = per_state ? (int64_t)bv.n_points * nq : 0;
+  const void* dpq = per_state ? st.in(bq.per_state, sizeof(T) * stride_q * B) : nullptr;
+  const void* dpv = per_state ? st.in(bv.per_state, sizeof(T) * stride_v * B) : nullptr;
   if (st.rc) return st.rc;
   std::vector<double> tab;
-  append_curve(tab, bq, nq);
-  append_curve(tab, bv, nq);
+  if (per_state) {
+    append_coeffs(tab, bq.n_points);
+    append_coeffs(tab, bv.n_points);
+  } else {
+    append_curve(tab, bq.one(), nq);
+    append_curve(tab, bv.one(), nq);
+  }
   // scratch: the torque law's, the desired state, the state rows the caller
   // did not ask for, and the curve table
   const int64_t chunk = std::min(B, kCtlChunk);
@@ -1282,8 +1314,19 @@ int control_rollout(ikg_model* model, int device, const void* q0, const void* v0
           a.t = o[2] ? row_at(o[2], sz[2], off) : stt;
           a.qdes = wqd;
           a.vdes = wvd;
-          a.cv = ikg::RolloutCurves{wtab,     bq.n_points, bv.n_points, bq.t_min, bq.t_max,
-                                    bq.mult,  bv.t_min,    bv.t_max,    bv.mult};
+          a.cv = ikg::RolloutCurves{wtab,
+                                    bq.n_points,
+                                    bv.n_points,
+                                    bq.t_min,
+                                    bq.t_max,
+                                    bq.mult,
+                                    bv.t_min,
+                                    bv.t_max,
+                                    bv.mult,
+                                    (const T*)row_at(dpq, stride_q, off),  // curves chunk with their states
+                                    (const T*)row_at(dpv, stride_v, off),
+                                    stride_q,
+                                    stride_v};
           a.dt_sim = params.dt_sim;
           a.dt_traj = params.dt_traj;
           a.q_hist = row_at(o[3], sz[3], off);
@@ -1306,6 +1349,47 @@ int control_rollout(ikg_model* model, int device, const void* q0, const void* v0
         });
       });
   return rc ? rc : st.finish();
+}
+
+// the arguments both rollout entries share, before their curves
+int check_rollout_args(const ikg_model* model, const void* q0, int64_t B, const ikg_rollout_params* params,
+                       const ikg_rollout_out* out) {
+  if (!model) return fail(IKG_EINVAL, "model is NULL");
+  if (!out) return fail(IKG_EINVAL, "out is NULL");
+  if (!params) return fail(IKG_EINVAL, "params is NULL");
+  if (B < 0) return fail(IKG_EINVAL, "B must be >= 0");
+  if (B > 0 && !q0) return fail(IKG_EINVAL, "q0 is required");
+  if (B > (int64_t)1 << 40) return fail(IKG_EINVAL, "B too large");
+  if (!model->ine.present) return fail(IKG_EINVAL, "%s", model->ine.missing);
+  return IKG_OK;
+}
+
+int check_bezier_set(const ikg_bezier_set* c, int dim, int64_t B, uint32_t flags, const char* what) {
+  if (!c || (B > 0 && !c->points)) return fail(IKG_EINVAL, "%s: curves or their points are NULL", what);
+  const double one = 0.0;  // check_bezier's rules for the sizes and the range
+  const ikg_bezier b{&one, c->n_points, c->t_min, c->t_max, c->mult};
+  if (int rc = check_bezier(&b, 0, what)) return rc;
+  return check_finite_rows<double>(flags, B, {{c->points, (int64_t)c->n_points * dim, what}});
+}
+
+// the rest of a rollout entry once its curves passed
+int rollout_entry(const ikg_model* model, int device, const void* q0, const void* v0, const void* t0, int64_t B,
+                  const CurveArg& bq, const CurveArg& bv, const ikg_rollout_params& params,
+                  const ikg_rollout_out& out, void* stream, uint32_t flags) {
+  const int nq = model->desc.nq;
+  const double dt[2] = {params.dt_sim, params.dt_traj};
+  int rc = check_control_params(params.control, dt);
+  if (rc) return rc;
+  if (params.ticks < 0 || params.record_every < 0) return fail(IKG_EINVAL, "ticks and record_every must be >= 0");
+  if ((out.q_hist || out.v_hist || out.tau_hist) && params.record_every == 0)
+    return fail(IKG_EINVAL, "a history output needs record_every > 0");
+  // (the device code is built with -ffinite-math-only)
+  if ((rc = check_finite_rows<double>(flags, B, {{q0, nq, "q0"}, {v0, nq, "v0"}, {t0, 1, "t0"}}))) return rc;
+  DeviceGuard g(device);
+  if (g.rc) return g.rc;
+  if (B == 0) return IKG_OK;
+  return control_rollout(const_cast<ikg_model*>(model), device, q0, v0, t0, B, bq, bv, params, out,
+                         (hipStream_t)stream, flags);
 }
 
 }  // namespace
@@ -1375,29 +1459,91 @@ int ikg_control_rollout(const ikg_model* model, int device, const void* q0, cons
                         const ikg_bezier* q_curve, const ikg_bezier* v_curve, const ikg_rollout_params* params,
                         const ikg_rollout_out* out, void* stream, uint32_t flags) {
   g_err[0] = 0;
-  if (!model) return fail(IKG_EINVAL, "model is NULL");
-  if (!out) return fail(IKG_EINVAL, "out is NULL");
-  if (!params) return fail(IKG_EINVAL, "params is NULL");
-  if (B < 0) return fail(IKG_EINVAL, "B must be >= 0");
-  if (B > 0 && !q0) return fail(IKG_EINVAL, "q0 is required");
-  if (B > (int64_t)1 << 40) return fail(IKG_EINVAL, "B too large");
-  if (!model->ine.present) return fail(IKG_EINVAL, "%s", model->ine.missing);
+  if (int rc = check_rollout_args(model, q0, B, params, out)) return rc;
   const int nq = model->desc.nq;
   int rc = check_bezier(q_curve, nq, "q_curve");
   if (!rc) rc = check_bezier(v_curve, nq, "v_curve");
   if (rc) return rc;
-  const double dt[2] = {params->dt_sim, params->dt_traj};
-  if ((rc = check_control_params(params->control, dt))) return rc;
-  if (params->ticks < 0 || params->record_every < 0) return fail(IKG_EINVAL, "ticks and record_every must be >= 0");
-  if ((out->q_hist || out->v_hist || out->tau_hist) && params->record_every == 0)
-    return fail(IKG_EINVAL, "a history output needs record_every > 0");
-  // (the device code is built with -ffinite-math-only)
-  if ((rc = check_finite_rows<double>(flags, B, {{q0, nq, "q0"}, {v0, nq, "v0"}, {t0, 1, "t0"}}))) return rc;
+  return rollout_entry(model, device, q0, v0, t0, B, CurveArg(*q_curve), CurveArg(*v_curve), *params, *out, stream,
+                       flags);
+}
+
+int ikg_control_rollout_curves(const ikg_model* model, int device, const void* q0, const void* v0, const void* t0,
+                               int64_t B, const ikg_bezier_set* q_curves, const ikg_bezier_set* v_curves,
+                               const ikg_rollout_params* params, const ikg_rollout_out* out, void* stream,
+                               uint32_t flags) {
+  g_err[0] = 0;
+  if (int rc = check_rollout_args(model, q0, B, params, out)) return rc;
+  const int nq = model->desc.nq;
+  int rc = check_bezier_set(q_curves, nq, B, flags, "q_curves");
+  if (!rc) rc = check_bezier_set(v_curves, nq, B, flags, "v_curves");
+  if (rc) return rc;
+  return rollout_entry(model, device, q0, v0, t0, B, CurveArg(*q_curves), CurveArg(*v_curves), *params, *out, stream,
+                       flags);
+}
+
+void ikg_fit_params_default(ikg_fit_params* p) {
+  if (!p) return;
+  p->degree = 20;  // control.py:85
+  p->ridge = 0.0;
+  p->total_time = 1.0;
+}
+
+int ikg_bezier_fit_batch(int device, const void* q0, const void* q1, const void* path_points, const int64_t* offsets,
+                         int64_t B, int32_t dim, const ikg_fit_params* params, void* points, void* vpoints,
+                         void* apoints, void* cost, int32_t* status, void* stream, uint32_t flags) {
+  g_err[0] = 0;
+  if (!params) return fail(IKG_EINVAL, "params is NULL");
+  if (dim < 1 || dim > IKG_MAX_NQ) return fail(IKG_EINVAL, "dim must be in [1, %d]", IKG_MAX_NQ);
+  const int d = params->degree;
+  if (d < ikg::kFitMinDegree || d > ikg::kFitMaxDegree)
+    return fail(IKG_EINVAL, "degree must be in [%d, %d]", ikg::kFitMinDegree, ikg::kFitMaxDegree);
+  if (!std::isfinite(params->total_time) || !(params->total_time > 0))
+    return fail(IKG_EINVAL, "total_time must be > 0");
+  if (!std::isfinite(params->ridge) || !(params->ridge >= 0)) return fail(IKG_EINVAL, "ridge must be >= 0 and finite");
+  if (B < 0) return fail(IKG_EINVAL, "B must be >= 0");
+  if (B > (int64_t)1 << 40) return fail(IKG_EINVAL, "B too large");
+  if (B > 0 && (!q0 || !q1 || !path_points || !offsets || !points || !cost || !status))
+    return fail(IKG_EINVAL, "q0, q1, path_points, offsets, points, cost and status are required");
+  int64_t total = 0;
+  if (flags & IKG_FLAG_HOST_POINTERS) {
+    if (B > 0 && offsets[0] != 0) return fail(IKG_EINVAL, "offsets[0] must be 0");
+    for (int64_t p = 0; p < B; ++p) {
+      const int64_t n = offsets[p + 1] - offsets[p];
+      if (n < 2 || n > ikg::kFitMaxN)
+        return fail(IKG_EINVAL, "path %lld has %lld points (2 .. %d)", (long long)p, (long long)n, ikg::kFitMaxN);
+      if (!ikg::fit_count_ok(n, d, params->ridge))
+        return fail(IKG_EINVAL, "path %lld has %lld points: degree %d needs %d unless ridge > 0", (long long)p,
+                    (long long)n, d, d - 3);
+    }
+    total = B > 0 ? offsets[B] : 0;
+    if (int rc = check_finite_rows<double>(flags, B, {{q0, dim, "q0"}, {q1, dim, "q1"}})) return rc;
+    if (int rc = check_finite<double>(path_points, total * dim, "path_points")) return rc;
+  }
   DeviceGuard g(device);
   if (g.rc) return g.rc;
   if (B == 0) return IKG_OK;
-  return control_rollout(const_cast<ikg_model*>(model), device, q0, v0, t0, B, *q_curve, *v_curve, *params, *out,
-                         (hipStream_t)stream, flags);
+  hipStream_t s = (hipStream_t)stream;
+  Staging st(s, flags);
+  ikg::FitArgs a;
+  a.q0 = (const double*)st.in(q0, sizeof(double) * dim * B);
+  a.q1 = (const double*)st.in(q1, sizeof(double) * dim * B);
+  a.y = (const double*)st.in(path_points, sizeof(double) * dim * total);
+  a.offsets = (const int64_t*)st.in(offsets, sizeof(int64_t) * (B + 1));
+  a.dim = dim;
+  a.degree = d;
+  a.ridge = params->ridge;
+  a.T = params->total_time;
+  a.points = (double*)st.out(points, sizeof(double) * (d + 1) * dim * B);
+  a.vpoints = (double*)st.out(vpoints, sizeof(double) * d * dim * B);
+  a.apoints = (double*)st.out(apoints, sizeof(double) * (d - 1) * dim * B);
+  a.cost = (double*)st.out(cost, sizeof(double) * B);
+  a.status = (int32_t*)st.out(status, sizeof(int32_t) * B);
+  if (st.rc) return st.rc;
+  ikg::bezier_coeffs(d + 1, a.bc);
+  const hipError_t e = ikg::launch_bezier_fit(a, B, s);
+  if (e != hipSuccess) return hip_fail(e, "ikg bezier fit kernel launch");
+  return st.finish();
 }
 
 }  // extern "C"

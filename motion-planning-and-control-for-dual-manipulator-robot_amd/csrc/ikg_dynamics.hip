@@ -410,10 +410,18 @@ struct TableChunk {
   double x[kTableChunk];
 };
 
-__device__ inline KBezier<double> curve_q(const RolloutCurves& cv, const double* tab, int nq) {
+// state p's curves over the table `tab` (RolloutCurves); PS: a curve pair per state.  A template parameter, not
+// a run-time branch: the shared-curve step kernel compiles as it did before the per-state entry existed.
+template <bool PS>
+__device__ inline KBezier<double> curve_q(const RolloutCurves& cv, const double* tab, int nq, int64_t p) {
+  if constexpr (PS)
+    return KBezier<double>{cv.pq + p * cv.stride_q, tab, cv.nq_pts, nq, cv.q_tmin, cv.q_tmax, cv.q_mult};
   return KBezier<double>{tab, tab + cv.nq_pts * nq, cv.nq_pts, nq, cv.q_tmin, cv.q_tmax, cv.q_mult};
 }
-__device__ inline KBezier<double> curve_v(const RolloutCurves& cv, const double* tab, int nq) {
+template <bool PS>
+__device__ inline KBezier<double> curve_v(const RolloutCurves& cv, const double* tab, int nq, int64_t p) {
+  if constexpr (PS)
+    return KBezier<double>{cv.pv + p * cv.stride_v, tab + cv.nq_pts, cv.nv_pts, nq, cv.v_tmin, cv.v_tmax, cv.v_mult};
   const double* tv = tab + (size_t)cv.nq_pts * (nq + 1);
   return KBezier<double>{tv, tv + cv.nv_pts * nq, cv.nv_pts, nq, cv.v_tmin, cv.v_tmax, cv.v_mult};
 }
@@ -473,7 +481,9 @@ __global__ __launch_bounds__(256) void ikg_rollout_init_kernel(const double* __r
   const double t = t0 ? t0[p] : a.cv.q_tmin;
   ((double*)a.q)[i] = q0[i];
   ((double*)a.v)[i] = v0 ? v0[i] : 0.0;
-  const KBezier<double> cq = curve_q(a.cv, a.cv.table, nq), cv = curve_v(a.cv, a.cv.table, nq);
+  const bool ps = a.cv.stride_q != 0;
+  const KBezier<double> cq = ps ? curve_q<true>(a.cv, a.cv.table, nq, p) : curve_q<false>(a.cv, a.cv.table, nq, p);
+  const KBezier<double> cv = ps ? curve_v<true>(a.cv, a.cv.table, nq, p) : curve_v<false>(a.cv, a.cv.table, nq, p);
   ((double*)a.qdes)[i] = bezier_eval(cq, bezier_clamp(cq, t), r);
   ((double*)a.vdes)[i] = bezier_eval(cv, bezier_clamp(cv, t), r);
   if (r == 0) ((double*)a.t)[p] = t;
@@ -494,9 +504,10 @@ hipError_t launch_rollout_init(const void* q0, const void* v0, const void* t0, i
 // factor of M the solve left in LDS the forward dynamics qdd = M^-1 (tau - nle),
 // the integrator, the trajectory clock, the desired state of the next tick
 // (Horner over the curves' control points, staged in LDS behind the states'
-// workspaces) and this tick's record.  Groups past the end of the batch work on
+// workspaces; with a curve pair per state only the binomial factors are staged
+// and each state reads its own control points) and this tick's record.  Groups past the end of the batch work on
 // the last state and store nothing.
-template <int G>
+template <int G, bool PS>
 __global__ __launch_bounds__(64) void ikg_control_step_kernel(CtlIn in, int nq, int64_t B, KCtl<double> prm,
                                                               StepArgs a) {
   using T = double;
@@ -511,7 +522,7 @@ __global__ __launch_bounds__(64) void ikg_control_step_kernel(CtlIn in, int nq, 
   ctl_ws_bind(base + (size_t)grp * step_ws_len(nq), nq, w);
   T* flag = base + (size_t)grp * step_ws_len(nq) + ctl_ws_len(nq);
   T* tab = base + (size_t)(64 / G) * step_ws_len(nq);
-  const int ntab = (nq + 1) * (a.cv.nq_pts + a.cv.nv_pts);
+  const int ntab = (int)rollout_table_len(nq, a.cv.nq_pts, a.cv.nv_pts, PS);
   for (int i = lane; i < ntab; i += 64) tab[i] = a.cv.table[i];
   ctl_ws_load_lanes(w, in, p, r, G);
   const bool row = live && r < nq;
@@ -530,7 +541,7 @@ __global__ __launch_bounds__(64) void ikg_control_step_kernel(CtlIn in, int nq, 
     step_integrate(a.dt_sim, f.qdd[r], q, v);
     ((T*)a.q)[p * nq + r] = q;
     ((T*)a.v)[p * nq + r] = v;
-    const KBezier<T> cq = curve_q(a.cv, tab, nq), cv = curve_v(a.cv, tab, nq);
+    const KBezier<T> cq = curve_q<PS>(a.cv, tab, nq, p), cv = curve_v<PS>(a.cv, tab, nq, p);
     ((T*)a.qdes)[p * nq + r] = bezier_eval(cq, bezier_clamp(cq, t), r);
     ((T*)a.vdes)[p * nq + r] = bezier_eval(cv, bezier_clamp(cv, t), r);
     if (a.slot >= 0) {
@@ -543,19 +554,30 @@ __global__ __launch_bounds__(64) void ikg_control_step_kernel(CtlIn in, int nq, 
   if (r == 0) ((T*)a.t)[p] = t;
 }
 
+namespace {
+
+template <int G, bool PS>
+hipError_t launch_step(unsigned nblocks, const CtlIn& in, int nq, int64_t B, const KCtl<double>& prm, const StepArgs& a,
+                       hipStream_t s) {
+  const size_t lds =
+      sizeof(double) * ((64 / G) * step_ws_len(nq) + rollout_table_len(nq, a.cv.nq_pts, a.cv.nv_pts, PS));
+  if (lds > 65536) {  // long curves on a wide model: above the default limit of dynamic LDS
+    const hipError_t e = hipFuncSetAttribute((const void*)ikg_control_step_kernel<G, PS>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL((ikg_control_step_kernel<G, PS>), dim3(nblocks), dim3(64), lds, s, in, nq, B, prm, a);
+  return hipGetLastError();
+}
+
+}  // namespace
+
 hipError_t launch_control_step(const CtlIn& in, int nq, int64_t B, const KCtl<double>& prm, const StepArgs& a,
                                hipStream_t s) {
   return launch_per_state(nq, B, [&](auto g, unsigned nblocks) {
     constexpr int G = decltype(g)::value;
-    const size_t lds =
-        sizeof(double) * ((64 / G) * step_ws_len(nq) + rollout_table_len(nq, a.cv.nq_pts, a.cv.nv_pts));
-    if (lds > 65536) {  // long curves on a wide model: above the default limit of dynamic LDS
-      const hipError_t e = hipFuncSetAttribute((const void*)ikg_control_step_kernel<G>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((ikg_control_step_kernel<G>), dim3(nblocks), dim3(64), lds, s, in, nq, B, prm, a);
-    return hipGetLastError();
+    return a.cv.stride_q != 0 ? launch_step<G, true>(nblocks, in, nq, B, prm, a, s)
+                              : launch_step<G, false>(nblocks, in, nq, B, prm, a, s);
   });
 }
 

@@ -5,13 +5,16 @@
 // GPU.  Built as libikgrasp_emu.so; used by tests/test_host_emu.py.  Further
 // down: the collision, dynamics, controller and closed-loop rollout arithmetic
 // on the same terms (tests/test_collision.py, test_dynamics.py, test_rollout.py).
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 #include "ikg_collision.hpp"
 #include "ikg_device.hpp"
 #include "ikg_dynamics.hpp"
+#include "ikg_fit.hpp"
 #include "ikg_model_build.hpp"
 #include "ikgrasp.h"
 
@@ -690,10 +693,12 @@ extern "C" int ikg_emu_bezier(const double* points, int32_t n_points, int32_t di
 
 // ikg_control_rollout on the CPU: per state and tick the kinematic terms
 // (above), dynamics_state and control_step_state, the clock and the curves.
-extern "C" int ikg_emu_control_rollout(const ikg_model_desc* d, const ikg_inertia_desc* id, const double* q0,
-                                       const double* v0, const double* t0, int64_t B, const ikg_bezier* bq,
-                                       const ikg_bezier* bv, const ikg_rollout_params* p,
-                                       const ikg_rollout_out* out) {
+// State i reads its control points at points + i stride (0 = one shared pair).
+namespace {
+
+int emu_rollout(const ikg_model_desc* d, const ikg_inertia_desc* id, const double* q0, const double* v0,
+                const double* t0, int64_t B, const ikg_bezier* bq, const ikg_bezier* bv, int64_t stride_q,
+                int64_t stride_v, const ikg_rollout_params* p, const ikg_rollout_out* out) {
   const EmuTables<double>* tb = emu_tables<double>(d, id);
   if (!tb) return -1;
   if (!emu_curve_ok(bq) || !emu_curve_ok(bv) || p->ticks < 0 || p->record_every < 0) return -1;
@@ -703,10 +708,10 @@ extern "C" int ikg_emu_control_rollout(const ikg_model_desc* d, const ikg_inerti
   double bcq[ikg::kMaxBezier], bcv[ikg::kMaxBezier];
   ikg::bezier_coeffs(bq->n_points, bcq);
   ikg::bezier_coeffs(bv->n_points, bcv);
-  const ikg::KBezier<double> cq{bq->points, bcq, bq->n_points, nq, bq->t_min, bq->t_max, bq->mult};
-  const ikg::KBezier<double> cv{bv->points, bcv, bv->n_points, nq, bv->t_min, bv->t_max, bv->mult};
   const int64_t every = p->record_every, R = every > 0 ? p->ticks / every : 0;
   for (int64_t i = 0; i < B; ++i) {
+    const ikg::KBezier<double> cq{bq->points + i * stride_q, bcq, bq->n_points, nq, bq->t_min, bq->t_max, bq->mult};
+    const ikg::KBezier<double> cv{bv->points + i * stride_v, bcv, bv->n_points, nq, bv->t_min, bv->t_max, bv->mult};
     double q[ikg::kMaxNq], v[ikg::kMaxNq], qd[ikg::kMaxNq], vd[ikg::kMaxNq], tau[ikg::kMaxNq];
     double t = t0 ? t0[i] : bq->t_min;
     for (int j = 0; j < nq; ++j) {
@@ -738,6 +743,73 @@ extern "C" int ikg_emu_control_rollout(const ikg_model_desc* d, const ikg_inerti
       if (out->v) ((double*)out->v)[nq * i + j] = v[j];
     }
     if (out->t) ((double*)out->t)[i] = t;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int ikg_emu_control_rollout(const ikg_model_desc* d, const ikg_inertia_desc* id, const double* q0,
+                                       const double* v0, const double* t0, int64_t B, const ikg_bezier* bq,
+                                       const ikg_bezier* bv, const ikg_rollout_params* p,
+                                       const ikg_rollout_out* out) {
+  return emu_rollout(d, id, q0, v0, t0, B, bq, bv, 0, 0, p, out);
+}
+
+// ikg_control_rollout_curves with host pointers on the CPU
+extern "C" int ikg_emu_control_rollout_curves(const ikg_model_desc* d, const ikg_inertia_desc* id, const double* q0,
+                                              const double* v0, const double* t0, int64_t B,
+                                              const ikg_bezier_set* sq, const ikg_bezier_set* sv,
+                                              const ikg_rollout_params* p, const ikg_rollout_out* out) {
+  if (!sq || !sv) return -1;
+  const ikg_bezier bq{(const double*)sq->points, sq->n_points, sq->t_min, sq->t_max, sq->mult};
+  const ikg_bezier bv{(const double*)sv->points, sv->n_points, sv->t_min, sv->t_max, sv->mult};
+  return emu_rollout(d, id, q0, v0, t0, B, &bq, &bv, (int64_t)sq->n_points * d->nq, (int64_t)sv->n_points * d->nq, p,
+                     out);
+}
+
+// ---------------------------------------------------------------- Bezier trajectory fit on the CPU
+// ikg_bezier_fit_batch: the phases of ikg_fit.hpp with a loop as their executor.
+// -1 where a host-pointer call of the entry returns IKG_EINVAL for its
+// parameters; a path whose count is out of range gets the kernel's answer
+// (status 1, cost NaN, points untouched).
+namespace {
+
+struct HostItems {
+  template <typename F>
+  void operator()(int count, F&& fn) {
+    for (int i = 0; i < count; ++i) fn(i);
+  }
+};
+
+}  // namespace
+
+extern "C" int ikg_emu_bezier_fit(const double* q0, const double* q1, const double* y, const int64_t* offsets,
+                                  int64_t B, int32_t dim, const ikg_fit_params* prm, double* points, double* vpoints,
+                                  double* apoints, double* cost, int32_t* status) {
+  if (!prm || dim < 1 || dim > IKG_MAX_NQ || prm->degree < ikg::kFitMinDegree || prm->degree > ikg::kFitMaxDegree)
+    return -1;
+  if (!(prm->total_time > 0) || !std::isfinite(prm->total_time) || !(prm->ridge >= 0) || !std::isfinite(prm->ridge))
+    return -1;
+  const int d = prm->degree;
+  double bc[ikg::kFitMaxDegree + 1];
+  ikg::bezier_coeffs(d + 1, bc);
+  std::vector<double> ws(ikg::fit_ws_len(d, dim));
+  ikg::FitWs w;
+  ikg::fit_ws_bind(ws.data(), d, dim, w);
+  HostItems ex;
+  for (int64_t p = 0; p < B; ++p) {
+    const int64_t n = offsets[p + 1] - offsets[p];
+    if (!ikg::fit_count_ok(n, d, prm->ridge)) {
+      status[p] = 1;
+      ikg::fit_store_nan(cost + p);
+      continue;
+    }
+    const ikg::FitPath f{q0 + p * dim, q1 + p * dim, y + offsets[p] * dim, (int)n, dim, d, prm->ridge,
+                         prm->total_time, bc};
+    cost[p] = ikg::bezier_fit_path(f, w, ex, points + p * (d + 1) * dim, vpoints ? vpoints + p * d * dim : nullptr,
+                                   apoints ? apoints + p * (d - 1) * dim : nullptr);
+    status[p] = 0;
   }
   return 0;
 }

@@ -576,14 +576,35 @@ hipError_t launch_control_solve(const CtlIn& in, int nq, int64_t B, const KCtl<d
 
 // closed-loop rollout (ikg_dynamics.hip).  The two curves' control points and
 // binomial factors sit in one device table: [Pq (nq_pts x nq)] [bcq (nq_pts)]
-// [Pv (nv_pts x nq)] [bcv (nv_pts)].
+// [Pv (nv_pts x nq)] [bcv (nv_pts)].  With a curve pair per state (stride != 0)
+// the table is the binomial factors alone, [bcq] [bcv], and state p's control
+// points are read where the caller keeps them: pq + p stride_q, pv + p stride_v.
 struct RolloutCurves {
   const double* table;
   int nq_pts, nv_pts;
   double q_tmin, q_tmax, q_mult;
   double v_tmin, v_tmax, v_mult;
+  const double *pq, *pv;       // per-state control points [n, n_pts, nq], else null
+  int64_t stride_q, stride_v;  // doubles between two states' curves; both 0 = one shared pair
 };
-inline size_t rollout_table_len(int nq, int nq_pts, int nv_pts) { return (size_t)(nq + 1) * (nq_pts + nv_pts); }
+IKG_HD inline size_t rollout_table_len(int nq, int nq_pts, int nv_pts, bool per_state = false) {
+  return (size_t)(per_state ? 1 : nq + 1) * (nq_pts + nv_pts);
+}
+
+// Bezier trajectory fit (ikg_fit.hip): all pointers device, fp64
+struct FitArgs {
+  const double *q0, *q1;   // [B,dim]
+  const double* y;         // packed path points [offsets[B],dim]
+  const int64_t* offsets;  // [B+1]
+  int dim, degree;
+  double ridge, T;
+  double* points;             // [B,degree+1,dim]
+  double *vpoints, *apoints;  // [B,degree,dim], [B,degree-1,dim] or null
+  double* cost;               // [B]
+  int32_t* status;            // [B]
+  double bc[21];              // bezier_coeffs(degree + 1)
+};
+hipError_t launch_bezier_fit(const FitArgs& args, int64_t B, hipStream_t s);
 
 // per-tick arguments of the step kernel (device, fp64): the state rows are
 // advanced in place, the desired state is rewritten for the next tick

@@ -127,6 +127,17 @@ class RolloutOut(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("q", "v", "t", "q_hist", "v_hist", "tau_hist")]
 
 
+class BezierSet(C.Structure):
+    """ikg_bezier_set: one curve per state, control points [B, n_points, nq] (device or host per flag)."""
+    _fields_ = [("points", C.c_void_p), ("n_points", C.c_int32), ("t_min", C.c_double), ("t_max", C.c_double),
+                ("mult", C.c_double)]
+
+
+class FitParams(C.Structure):
+    """ikg_fit_params: degree, ridge and total time of ikg_bezier_fit_batch."""
+    _fields_ = [("degree", C.c_int32), ("ridge", C.c_double), ("total_time", C.c_double)]
+
+
 EXPORTS = [
     "ikg_model_create", "ikg_model_destroy", "ikg_params_default", "ikg_solve_batch",
     "ikg_solve_multistart", "ikg_fk_batch", "ikg_log6_batch", "ikg_last_error", "ikg_version",
@@ -134,6 +145,7 @@ EXPORTS = [
     "ikg_frame_kinematics_batch", "ikg_model_specialize", "ikg_model_is_specialized", "ikg_model_trim",
     "ikg_model_set_inertia", "ikg_dynamics_batch", "ikg_control_params_default", "ikg_control_torque_batch",
     "ikg_forward_dynamics_batch", "ikg_bezier_eval_batch", "ikg_rollout_params_default", "ikg_control_rollout",
+    "ikg_control_rollout_curves", "ikg_fit_params_default", "ikg_bezier_fit_batch",
 ]
 
 _lib = None
@@ -216,6 +228,14 @@ def load() -> C.CDLL:
     lib.ikg_control_rollout.argtypes = [vp, i32, vp, vp, vp, i64, C.POINTER(Bezier), C.POINTER(Bezier),
                                         C.POINTER(RolloutParams), C.POINTER(RolloutOut), vp, C.c_uint32]
     lib.ikg_control_rollout.restype = i32
+    lib.ikg_control_rollout_curves.argtypes = [vp, i32, vp, vp, vp, i64, C.POINTER(BezierSet), C.POINTER(BezierSet),
+                                               C.POINTER(RolloutParams), C.POINTER(RolloutOut), vp, C.c_uint32]
+    lib.ikg_control_rollout_curves.restype = i32
+    lib.ikg_fit_params_default.argtypes = [C.POINTER(FitParams)]
+    lib.ikg_fit_params_default.restype = None
+    lib.ikg_bezier_fit_batch.argtypes = [i32, vp, vp, vp, vp, i64, C.c_int32, C.POINTER(FitParams), vp, vp, vp, vp, vp,
+                                         vp, C.c_uint32]
+    lib.ikg_bezier_fit_batch.restype = i32
     lib.ikg_model_specialize.argtypes = [vp, i32, i32, C.c_uint32]
     lib.ikg_model_specialize.restype = i32
     lib.ikg_model_is_specialized.argtypes = [vp, i32, i32]
@@ -333,6 +353,13 @@ def bezier_desc(traj, dim=None):
     if dim is not None and pts.shape[1] != dim:
         raise ValueError(f"control points have {pts.shape[1]} columns, the model has {dim} joints")
     return Bezier(pts.ctypes.data, pts.shape[0], t_min, t_max, mult), pts
+
+
+def fit_params(degree=20, ridge=0.0, total_time=1.0) -> FitParams:
+    p = FitParams()
+    load().ikg_fit_params_default(C.byref(p))
+    p.degree, p.ridge, p.total_time = int(degree), float(ridge), float(total_time)
+    return p
 
 
 def rollout_params(ticks, dt_sim=1e-3, dt_traj=1e-2, record_every=0, **gains) -> RolloutParams:

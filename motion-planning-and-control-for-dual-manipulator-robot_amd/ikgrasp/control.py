@@ -21,7 +21,9 @@ for many states in one launch of `ikg_dynamics_batch`, and
 `control_torques_batch` the whole second half of the law (:284-406: the
 operational-space inertia, the unconstrained QP and the torque line) through
 `ikg_control_torque_batch`.  `controllaw` is the drop-in for the reference
-function.  `rollout` runs B closed loops of that law against a free-space
+function.  `maketraj` is the drop-in for the reference's trajectory fit
+(control.py:63-197) and `maketraj_batch` fits B paths in one launch of
+`ikg_bezier_fit_batch`; `save_trajectory` writes the reference's file.  `rollout` runs B closed loops of that law against a free-space
 rigid-body plant in one call of `ikg_control_rollout` (desired state from the
 Bezier curves, torque law, forward dynamics, semi-implicit Euler), and
 `Simulation` is the same plant one tick at a time behind the simulator's
@@ -158,11 +160,105 @@ def load_trajectory(path):
                  for k in ("q_control_points", "vq_control_points", "vvq_control_points"))
 
 
+def save_trajectory(path, trajs):
+    """The reference's save_trajectory_to_json (control.py:203-215): the three
+    curves' control points and the q curve's t_min, t_max, mult_t.  The file
+    does not store the derivatives' multipliers, so `load_trajectory` gives
+    every curve the file's mult_t (its documented quirk)."""
+    q_of_t, vq_of_t, vvq_of_t = trajs
+    pts = lambda c: [np.asarray(p, dtype=np.float64).tolist() for p in c.control_points_]
+    with open(path, "w") as f:
+        json.dump({"q_control_points": pts(q_of_t), "vq_control_points": pts(vq_of_t),
+                   "vvq_control_points": pts(vvq_of_t), "t_min": q_of_t.T_min_, "t_max": q_of_t.T_max_,
+                   "mult_t": q_of_t.mult_T_}, f, indent=4)
+
+
+FIT_MAX_POINTS = 256  # ikg_bezier_fit_batch: path points per path
+FLAG_COST = 0.15      # control.py:191: `result.fun < 0.15`
+
+
+class FittedTrajectories:
+    """B fitted trajectories (`maketraj_batch`): points [B,degree+1,nq],
+    vpoints [B,degree,nq] and apoints [B,degree-1,nq] (the unscaled derivative
+    control points), cost [B], ok [B] = cost < 0.15 (the reference's flag),
+    t_min = 0 and t_max = total_time.  `curves(i)` is path i's (q_of_t,
+    vq_of_t, vvq_of_t); `rollout` takes the object as `trajs`."""
+
+    def __init__(self, points, vpoints, apoints, cost, total_time):
+        self.points, self.vpoints, self.apoints, self.cost = points, vpoints, apoints, cost
+        self.ok = cost < FLAG_COST
+        self.t_min, self.t_max = 0.0, float(total_time)
+
+    def __len__(self):
+        return len(self.points)
+
+    def curves(self, i):
+        q_of_t = Curve(list(self.points[i]), self.t_min, self.t_max)
+        return q_of_t, q_of_t.derivative(1), q_of_t.derivative(2)
+
+
+def maketraj_batch(q0s, q1s, paths, total_time, degree=20, ridge=None, solver=None):
+    """The reference's maketraj (control.py:63-197) for B paths in one launch of
+    `ikg_bezier_fit_batch` (GPU, fp64).  The reference's six equality
+    constraints pin three control points at each end; the remaining degree - 5
+    are a linear least-squares problem, which the kernel solves exactly
+    (SLSQP with finite-difference gradients stops early: the cost here is never
+    above the reference's).  q0s, q1s [B,nq]; paths: B arrays [n_i, nq],
+    2 <= n_i <= 256, packed here on the host.
+    ridge=None: 0 when every path has n >= degree - 3 points (the reference's
+    problem, 17 at degree 20), else 1e-10: a shorter path leaves the
+    reference's problem underdetermined and the ridge term picks the solution
+    nearest its initial guess linspace(q0, q1).  A ridge > 0 also damps the
+    large control polygons an exact fit of a noisy path produces.
+    `solver`: whose `bezier_fit` runs (an IKSolver: its device); default device 0.
+    -> FittedTrajectories."""
+    from . import solver as _solver
+    paths = [np.asarray(p, dtype=np.float64) for p in paths]
+    q0s = np.asarray(q0s, dtype=np.float64)
+    q0s = q0s.reshape(len(paths), -1)
+    nq = q0s.shape[1]
+    for i, p in enumerate(paths):
+        if p.ndim != 2 or p.shape[1] != nq:
+            raise ValueError(f"path {i} must be [n, {nq}], got {list(p.shape)}")
+        if not 2 <= len(p) <= FIT_MAX_POINTS:
+            raise ValueError(f"path {i} has {len(p)} points (2 .. {FIT_MAX_POINTS})")
+    if ridge is None:
+        ridge = 0.0 if all(len(p) >= degree - 3 for p in paths) else 1e-10
+    offsets = np.concatenate([[0], np.cumsum([len(p) for p in paths])]).astype(np.int64)
+    packed = np.concatenate(paths) if paths else np.zeros((0, nq))
+    fit = solver.bezier_fit if solver is not None else _solver.bezier_fit
+    r = fit(q0s, q1s, packed, offsets, total_time=total_time, degree=degree, ridge=ridge)
+    return FittedTrajectories(r["points"], r["vpoints"], r["apoints"], r["cost"], total_time)
+
+
+def maketraj(q0, q1, path_points, total_time, ridge=None, solver=None):
+    """Drop-in for the reference's `maketraj(q0, q1, path_points, total_time)`
+    (control.py:63-197) -> ([q_of_t, vq_of_t, vvq_of_t], flag): the degree-20
+    curve through `maketraj_batch` with B = 1, its derivatives exactly
+    q_of_t.derivative(1) and .derivative(2), flag = cost < 0.15 (:191).
+    ridge=None: 0 for 17 points or more, 1e-10 below (see maketraj_batch).
+    More than 256 points raise ValueError.  The reference's prints and its
+    trajectory2.json side effect are not reproduced (`save_trajectory`)."""
+    fitted = maketraj_batch([q0], [q1], [path_points], total_time, degree=20, ridge=ridge, solver=solver)
+    return list(fitted.curves(0)), bool(fitted.ok[0])
+
+
 def rollout(robot, q0, vq0, trajs, t0=None, ticks=1500, **kw):
     """B closed loops of `controllaw` against the free rigid-body plant in one
     call (`IKSolver.rollout`, GPU, fp64): trajs = (q_of_t, vq_of_t[, ...]) as
     the reference passes them; dt_sim, dt_traj, record_every, outputs and the
-    gains as keywords.  1,500 ticks are the reference's 15 s run."""
+    gains as keywords.  1,500 ticks are the reference's 15 s run.
+    One trajectory per state (`ikg_control_rollout_curves`): trajs = a
+    `FittedTrajectories`, or (points [B,n,nq], vpoints [B,n-1,nq], t_min,
+    t_max) with the unscaled derivative points; the v curves get
+    Bezier.derivative's multiplier 1 / (t_max - t_min)."""
+    if isinstance(trajs, FittedTrajectories):
+        trajs = (trajs.points, trajs.vpoints, trajs.t_min, trajs.t_max)
+    if len(trajs) == 4 and getattr(trajs[0], "ndim", 0) == 3:
+        points, vpoints, t_min, t_max = trajs
+        t_min, t_max = float(t_min), float(t_max)
+        sets = ((points, t_min, t_max, 1.0), (vpoints, t_min, t_max, 1.0 * (1.0 / (t_max - t_min))))
+        return robot.solver.rollout(q0, vq0, sets, t0=t0, ticks=ticks, per_state=True, **kw)
     return robot.solver.rollout(q0, vq0, (trajs[0], trajs[1]), t0=t0, ticks=ticks, **kw)
 
 

@@ -534,8 +534,14 @@ class IKSolver:
 
     ROLLOUT_OUTPUTS = ("q", "v", "t", "q_hist", "v_hist", "tau_hist")
 
+    def bezier_fit(self, q0, q1, path_points, offsets, total_time=1.0, degree=20, ridge=0.0, derivatives=True,
+                   stream=None) -> dict:
+        """ikg_bezier_fit_batch on this solver's device: see the module's `bezier_fit`."""
+        return bezier_fit(q0, q1, path_points, offsets, total_time=total_time, degree=degree, ridge=ridge,
+                          derivatives=derivatives, device=self.device, stream=stream)
+
     def rollout(self, q0, v0, trajs, t0=None, ticks=0, dt_sim=1e-3, dt_traj=1e-2, record_every=0,
-                outputs=("q", "v", "t"), stream=None, **gains) -> dict:
+                outputs=("q", "v", "t"), stream=None, per_state=False, **gains) -> dict:
         """ikg_control_rollout (fp64): `ticks` closed-loop ticks of B states in
         one call: desired state from the curves, the torque law, forward
         dynamics, semi-implicit Euler, clock.  The plant is the free rigid-body
@@ -547,18 +553,38 @@ class IKSolver:
         trajectory clock's step per tick (the reference's DT = 0.01 per 1 ms
         tick).  outputs: final q, v [B,nq], t [B]; with record_every > 0
         q_hist, v_hist, tau_hist [B, ticks // record_every, nq].
-        `gains` as control_torques."""
+        `gains` as control_torques.
+        per_state=True (ikg_control_rollout_curves): state p follows its own
+        curve pair; trajs = ((points [B,n,nq], t_min, t_max, mult), (vpoints
+        [B,n',nq], t_min, t_max, mult)) with arrays of q0's kind (numpy, or
+        float64 tensors on q0's device).  B equal curves give the shared-curve
+        result bit for bit."""
         unknown = set(outputs) - set(self.ROLLOUT_OUTPUTS)
         if unknown:
             raise ValueError(f"unknown outputs {sorted(unknown)}")
         nq = self.nq
-        bq, keep_q = _lib.bezier_desc(trajs[0], nq)
-        bv, keep_v = _lib.bezier_desc(trajs[1], nq)
         prm = _lib.rollout_params(ticks, dt_sim, dt_traj, record_every, **gains)
         prep, empty, ptr, s, device, flags = self._f64_io(q0, stream)
         qq, vv = prep(q0, nq), prep(v0, nq)
         tt = None if t0 is None else prep(t0, 1)
         B = qq.shape[0]
+        if per_state:
+            sets, keep = [], []
+            for name, (pts, t_min, t_max, mult) in zip(("q", "v"), trajs):
+                if _is_torch(pts) != _is_torch(qq):
+                    raise ValueError(f"the {name} curves must be the same kind of array as q0")
+                if pts.ndim != 3 or pts.shape[0] != B or pts.shape[2] != nq:
+                    raise ValueError(f"the {name} curves must be [{B}, n_points, {nq}], got {list(pts.shape)}")
+                n_points = int(pts.shape[1])
+                flat = prep(pts, n_points * nq)
+                keep.append(flat)
+                sets.append(_lib.BezierSet(ptr(flat), n_points, float(t_min), float(t_max), float(mult)))
+            entry, bq, bv = self.lib.ikg_control_rollout_curves, sets[0], sets[1]
+        else:
+            bq, keep_q = _lib.bezier_desc(trajs[0], nq)
+            bv, keep_v = _lib.bezier_desc(trajs[1], nq)
+            keep = (keep_q, keep_v)
+            entry = self.lib.ikg_control_rollout
         if vv is not None and vv.shape[0] != B:
             raise ValueError(f"v0 has {vv.shape[0]} rows, q0 has {B}")
         if tt is not None and tt.shape[0] != B:
@@ -569,7 +595,66 @@ class IKSolver:
         shape = lambda k: (B,) if k == "t" else ((B, R, nq) if k.endswith("_hist") else (B, nq))
         res = {k: empty(*shape(k)) for k in outputs}
         out = _lib.RolloutOut(*[ptr(res.get(k)) for k in self.ROLLOUT_OUTPUTS])
-        _lib.check(self.lib.ikg_control_rollout(self._h, device, ptr(qq), ptr(vv), ptr(tt), B, C.byref(bq), C.byref(bv),
-                                                C.byref(prm), C.byref(out), s, flags))
-        del keep_q, keep_v
+        _lib.check(entry(self._h, device, ptr(qq), ptr(vv), ptr(tt), B, C.byref(bq), C.byref(bv), C.byref(prm),
+                         C.byref(out), s, flags))
+        del keep
         return res
+
+
+def bezier_fit(q0, q1, path_points, offsets, total_time=1.0, degree=20, ridge=0.0, derivatives=True, device=0,
+               stream=None) -> dict:
+    """ikg_bezier_fit_batch (fp64): the reference's maketraj (control.py:63-197)
+    for B paths in one launch, solved exactly (Householder least squares on the
+    degree - 5 control points its constraints leave free).
+    q0, q1 [B,dim]; path_points packed [offsets[B],dim]; offsets [B+1] int64,
+    offsets[0] = 0.  All numpy, or all ROCm tensors (float64, offsets int64):
+    then nothing leaves the device and no limit but the parameters' is checked
+    on the host; a path whose count is out of range gets status 1, cost NaN.
+    -> dict of points [B,degree+1,dim], cost [B], status [B] (int32) and, with
+    `derivatives`, vpoints [B,degree,dim], apoints [B,degree-1,dim]: the
+    unscaled derivative control points (Bezier.derivative's, without its
+    1 / total_time multiplier).  No model is involved."""
+    lib = _lib.load()
+    prm = _lib.fit_params(degree, ridge, total_time)
+    d = int(degree)
+    if _is_torch(q0):
+        import torch
+        dev = q0.device
+        if not q0.is_cuda or q0.dtype != torch.float64:
+            raise ValueError("torch inputs must be float64 tensors on a ROCm device (or pass numpy arrays)")
+        if not (_is_torch(offsets) and offsets.is_cuda and offsets.dtype == torch.int64):
+            raise ValueError("with tensor inputs offsets must be an int64 tensor on the same device")
+        dim = int(q0.shape[-1])
+        a0, a1 = q0.contiguous().view(-1, dim), q1.to(device=dev, dtype=torch.float64).contiguous().view(-1, dim)
+        yy = path_points.to(device=dev, dtype=torch.float64).contiguous().view(-1, dim)
+        off = offsets.contiguous()
+        empty = lambda *shape, dtype=torch.float64: torch.empty(shape, dtype=dtype, device=dev)
+        i32 = torch.int32
+        ptr = lambda x: None if x is None else x.data_ptr()
+        s = C.c_void_p(stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream)
+        device, flags = dev.index or 0, 0
+    else:
+        a0 = np.ascontiguousarray(q0, dtype=np.float64)
+        dim = int(a0.shape[-1])
+        a0 = a0.reshape(-1, dim)
+        a1 = np.ascontiguousarray(q1, dtype=np.float64).reshape(-1, dim)
+        yy = np.ascontiguousarray(path_points, dtype=np.float64).reshape(-1, dim)
+        off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if len(off) and int(off[-1]) != len(yy):
+            raise ValueError(f"offsets end at {int(off[-1])}, path_points has {len(yy)} rows")
+        empty = lambda *shape, dtype=np.float64: np.empty(shape, dtype=dtype)
+        i32 = np.int32
+        ptr = lambda x: None if x is None else x.ctypes.data
+        s, flags = None, _lib.IKG_FLAG_HOST_POINTERS
+    B = a0.shape[0]
+    if a1.shape[0] != B or off.shape[0] != B + 1:
+        raise ValueError(f"q0 has {B} rows: q1 needs {B} and offsets {B + 1} entries")
+    if not 6 <= d <= 20:
+        raise ValueError("degree must be in [6, 20]")
+    res = {"points": empty(B, d + 1, dim), "cost": empty(B), "status": empty(B, dtype=i32)}
+    if derivatives:
+        res["vpoints"], res["apoints"] = empty(B, d, dim), empty(B, d - 1, dim)
+    _lib.check(lib.ikg_bezier_fit_batch(device, ptr(a0), ptr(a1), ptr(yy), ptr(off), B, dim, C.byref(prm),
+                                        ptr(res["points"]), ptr(res.get("vpoints")), ptr(res.get("apoints")),
+                                        ptr(res["cost"]), ptr(res["status"]), s, flags))
+    return res
