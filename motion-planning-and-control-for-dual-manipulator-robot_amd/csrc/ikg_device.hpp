@@ -809,7 +809,10 @@ IKG_HD inline void log6_iter(const T* R, const T* p, T* e, ThetaTrack<T>* tk = n
   T theta = T(0);
   if constexpr (is_f64<T>) {
     bool exact = true;
-    if (tk && (COLD ? __builtin_expect(!resync, true) : !resync)) {
+    // COLD: the increment runs on every update, resyncs (1 in kResync) included, with no branch
+    // of its own: there `exact` is set for every lane below, so the select discards it (tk is
+    // zero-initialised: update 0 reads finite values)
+    if (tk && (COLD || !resync)) {
       const T y = st * tk->ct - ct * tk->st;  // rho sin(theta - theta_prev)
       const T x = ct * tk->ct + st * tk->st;  // rho cos(theta - theta_prev)
 #if IKG_THETA_ASIN
@@ -821,6 +824,7 @@ IKG_HD inline void log6_iter(const T* R, const T* p, T* e, ThetaTrack<T>* tk = n
       exact = !(fabs(y) <= ThetaInc<T>::kInc * x);
       theta = tk->th + ThetaInc<T>::atan_small(fdiv<T>(y, fmax(x, T(1e-30))));
 #endif
+      if constexpr (COLD) exact = exact || resync;
     }
     if (IKG_RARELY(COLD, wave_any<T>(exact))) {
 #if IKG_THETA == 1

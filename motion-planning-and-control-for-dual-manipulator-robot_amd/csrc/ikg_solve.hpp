@@ -321,7 +321,7 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
   int stop_at = prm.max_iters;  // RETIRE: the count at which the loop leaves
   // RETIRE: it % kResync, formed once per update for the trig advance and carried to the next
   // update's FK (a bool carried round the loop becomes a lane mask, so the count is carried)
-  int rs_phase = 0;
+  unsigned rs_phase = 0;
   T sn[7], cs[7];
   int it = 0;
   ThetaTrack<T> tk{};
@@ -572,7 +572,10 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
 #endif
     if constexpr (F1) {
       // RETIRE: one resync predicate per update, this advance's is the next update's
-      if constexpr (RETIRE) rs_phase = it % Trig<T>::kResync;
+      // (a mask of the unsigned count: the signed modulo was five scalar instructions)
+      static_assert(!RETIRE || (Trig<T>::kResync & (Trig<T>::kResync - 1)) == 0,
+                    "the resync period is a power of two");
+      if constexpr (RETIRE) rs_phase = (unsigned)it & (unsigned)(Trig<T>::kResync - 1);
       const bool rs = RETIRE ? rs_phase == 0 : (it % (REC ? kRsRec<T> : Trig<T>::kResync)) == 0;
       trig_advance_f1<T, MED, COLD>(m, arm, qc, qa, q_old, rs, sn, cs);
 #ifdef IKG_STAGE_CLOCK
