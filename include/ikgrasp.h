@@ -579,6 +579,57 @@ int ikg_bezier_fit_batch(int device, const void* q0, const void* q1, const void*
                          int64_t B, int32_t dim, const ikg_fit_params* params, void* points, void* vpoints,
                          void* apoints, void* cost, int32_t* status, void* stream, uint32_t flags);
 
+/* ---- RRT-Connect planner primitives (path.py:125-278) ----
+ * fp64 only (the planner's IK is fp64).  All arrays are device arrays, or host
+ * arrays with IKG_FLAG_HOST_POINTERS (staged, checked for finiteness, the call
+ * returns after the results are back).  With device pointers the calls are
+ * stream-ordered and return without waiting.
+ *
+ * ikg_se3_interpolate_batch: pin.SE3.Interpolate for C placement pairs,
+ *   out[c] = A[c] * exp6(alpha[c] * log6(A[c]^-1 B[c])),  A, B, out [C,12], alpha [C]
+ * with Pinocchio's branches (log6 as ikg_log6_batch; exp6's Taylor series below
+ * eps^(1/4)).  Rotations of A^-1 B within 0.01 rad of pi are not pinned.
+ *
+ * ikg_nearest_batch: the nearest node of P trees.  Tree p is the rows
+ * nodes[p * cap .. p * cap + counts[p] - 1], each of length nq; rows at and
+ * past counts[p] are never read as candidates.  index[p] is the row with the
+ * least Euclidean distance to queries[p] (the squared distance summed over
+ * j = 0 .. nq-1 in that order), the LOWEST index among exact ties; dist[p] the
+ * square root of that sum.  counts[p] == 0 gives index -1 (dist 0).  A
+ * host-pointer call rejects counts outside [0, cap]; with device pointers a
+ * count above cap is read as cap.
+ *   nodes [P,cap,nq], counts [P] int32, queries [P,nq], index [P] int32, dist [P]
+ *
+ * ikg_project_paths: path.py:125-163 (project_path) for C chains advanced in
+ * lock-step.  Chain c interpolates cube_curr[c] -> cube_rand[c] in
+ * steps = int(|dt| / step_size) + 1 steps; at step s it places the cube at
+ * Interpolate(s / steps), checks the scene's target geometry there against the
+ * listed world-fixed geometries (the narrow phase of ikg_target_env_batch),
+ * solves the IK warm-started from its last accepted q (ikg_solve_batch with
+ * `params`; the planner sets check_collision = 1) and appends (q, placement)
+ * when the placement is free and the solve converged; otherwise the chain stops.
+ *   q_curr [C,nq], cube_curr, cube_rand [C,12], geoms [n_geoms] (HOST array)
+ *   robot_path [C,max_nodes,nq], cube_path [C,max_nodes,12]: row 0 is q_curr /
+ *     cube_curr, rows 1 .. n_nodes[c]-1 the accepted steps; later rows are
+ *     unspecified (zero with host pointers)
+ *   n_nodes [C] int32, status [C] int32:
+ *     0 reached cube_rand, 1 stopped by a placement collision, 2 stopped by a
+ *     failed IK, 3 cut at max_nodes (status holds -1 while a chain advances)
+ * Per step a prepare kernel, the solve and a commit kernel are enqueued on
+ * `stream`; nothing waits on the host.  A host-pointer call enqueues as many
+ * steps as its longest chain needs, a device-pointer call max_nodes - 1.  The
+ * scratch is stream-ordered (the model's pool).  Not capturable.  Needs
+ * ikg_model_set_collision with a target geometry.  C == 0 is a no-op.
+ */
+int ikg_se3_interpolate_batch(int device, const void* A, const void* B, const void* alpha, int64_t C, void* out,
+                              void* stream, uint32_t flags);
+int ikg_nearest_batch(int device, const void* nodes, int64_t cap, const int32_t* counts, const void* queries,
+                      int32_t nq, int64_t P, int32_t* index, void* dist, void* stream, uint32_t flags);
+int ikg_project_paths(const ikg_model* model, int device, const void* q_curr, const void* cube_curr,
+                      const void* cube_rand, int64_t C, double step_size, int32_t max_nodes, const int32_t* geoms,
+                      int32_t n_geoms, const ikg_params* params, void* robot_path, void* cube_path, int32_t* n_nodes,
+                      int32_t* status, void* stream, uint32_t flags);
+
 /* Thread-local message of the last failure ("" if none). */
 const char* ikg_last_error(void);
 

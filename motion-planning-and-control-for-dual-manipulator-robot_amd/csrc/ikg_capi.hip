@@ -19,6 +19,7 @@
 #include "ikg_launch.hpp"
 #include "ikg_fit.hpp"
 #include "ikg_model_build.hpp"
+#include "ikg_planner.hpp"
 #include "ikgrasp.h"
 
 namespace {
@@ -1543,6 +1544,160 @@ int ikg_bezier_fit_batch(int device, const void* q0, const void* q1, const void*
   ikg::bezier_coeffs(d + 1, a.bc);
   const hipError_t e = ikg::launch_bezier_fit(a, B, s);
   if (e != hipSuccess) return hip_fail(e, "ikg bezier fit kernel launch");
+  return st.finish();
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------ RRT-Connect planner (ikg_planner.hpp)
+extern "C" {
+
+int ikg_se3_interpolate_batch(int device, const void* A, const void* B, const void* alpha, int64_t C, void* out,
+                              void* stream, uint32_t flags) {
+  g_err[0] = 0;
+  if (C < 0) return fail(IKG_EINVAL, "C must be >= 0");
+  if (C > (int64_t)1 << 40) return fail(IKG_EINVAL, "C too large");
+  if (C > 0 && (!A || !B || !alpha || !out)) return fail(IKG_EINVAL, "A, B, alpha and out are required");
+  if (int rc = check_finite_rows<double>(flags, C, {{A, 12, "A"}, {B, 12, "B"}, {alpha, 1, "alpha"}})) return rc;
+  DeviceGuard g(device);
+  if (g.rc) return g.rc;
+  if (C == 0) return IKG_OK;
+  hipStream_t s = (hipStream_t)stream;
+  Staging st(s, flags);
+  const double* dA = (const double*)st.in(A, sizeof(double) * 12 * C);
+  const double* dB = (const double*)st.in(B, sizeof(double) * 12 * C);
+  const double* da = (const double*)st.in(alpha, sizeof(double) * C);
+  double* dout = (double*)st.out(out, sizeof(double) * 12 * C);
+  if (st.rc) return st.rc;
+  const hipError_t e = ikg::launch_se3_interpolate(dA, dB, da, C, dout, s);
+  if (e != hipSuccess) return hip_fail(e, "ikg se3 interpolate kernel launch");
+  return st.finish();
+}
+
+int ikg_nearest_batch(int device, const void* nodes, int64_t cap, const int32_t* counts, const void* queries,
+                      int32_t nq, int64_t P, int32_t* index, void* dist, void* stream, uint32_t flags) {
+  g_err[0] = 0;
+  if (P < 0) return fail(IKG_EINVAL, "P must be >= 0");
+  if (P > kMaxWaves) return fail(IKG_EINVAL, "P=%lld too large for one launch (at most %lld)", (long long)P, (long long)kMaxWaves);
+  if (cap < 0 || cap > INT32_MAX) return fail(IKG_EINVAL, "cap must be in [0, 2^31)");
+  if (nq < 1) return fail(IKG_EINVAL, "nq must be >= 1");
+  if (P > 0 && (!counts || !queries || !index || !dist || (cap > 0 && !nodes)))
+    return fail(IKG_EINVAL, "nodes, counts, queries, index and dist are required");
+  if (flags & IKG_FLAG_HOST_POINTERS) {
+    for (int64_t p = 0; p < P; ++p) {
+      if (counts[p] < 0 || counts[p] > cap)
+        return fail(IKG_EINVAL, "counts[%lld] = %d outside [0, cap = %lld]", (long long)p, counts[p], (long long)cap);
+      if (int rc = check_finite<double>((const double*)nodes + p * cap * nq, (int64_t)counts[p] * nq, "nodes")) return rc;
+    }
+    if (int rc = check_finite<double>(queries, P * nq, "queries")) return rc;
+  }
+  DeviceGuard g(device);
+  if (g.rc) return g.rc;
+  if (P == 0) return IKG_OK;
+  hipStream_t s = (hipStream_t)stream;
+  Staging st(s, flags);
+  const double* dn = (const double*)st.in(nodes, sizeof(double) * P * cap * nq);
+  const int32_t* dc = (const int32_t*)st.in(counts, sizeof(int32_t) * P);
+  const double* dq = (const double*)st.in(queries, sizeof(double) * P * nq);
+  int32_t* di = (int32_t*)st.out(index, sizeof(int32_t) * P);
+  double* dd = (double*)st.out(dist, sizeof(double) * P);
+  if (st.rc) return st.rc;
+  const hipError_t e = ikg::launch_nearest(dn, cap, dc, dq, nq, P, di, dd, s);
+  if (e != hipSuccess) return hip_fail(e, "ikg nearest kernel launch");
+  return st.finish();
+}
+
+int ikg_project_paths(const ikg_model* model, int device, const void* q_curr, const void* cube_curr,
+                      const void* cube_rand, int64_t C, double step_size, int32_t max_nodes, const int32_t* geoms,
+                      int32_t n_geoms, const ikg_params* params, void* robot_path, void* cube_path, int32_t* n_nodes,
+                      int32_t* status, void* stream, uint32_t flags) {
+  g_err[0] = 0;
+  if (!model) return fail(IKG_EINVAL, "model is NULL");
+  if (C < 0) return fail(IKG_EINVAL, "C must be >= 0");
+  if (C > kMaxWaves) return fail(IKG_EINVAL, "C=%lld too large for one launch (at most %lld)", (long long)C, (long long)kMaxWaves);
+  if (!(step_size > 0) || !std::isfinite(step_size)) return fail(IKG_EINVAL, "step_size must be > 0");
+  if (max_nodes < 1) return fail(IKG_EINVAL, "max_nodes must be >= 1");
+  if (n_geoms < 1 || n_geoms > IKG_MAX_GEOMS || !geoms) return fail(IKG_EINVAL, "geoms must list 1 .. %d geometries", IKG_MAX_GEOMS);
+  if (int rc = check_params(params)) return rc;
+  if (C > 0 && (!q_curr || !cube_curr || !cube_rand || !robot_path || !cube_path || !n_nodes || !status))
+    return fail(IKG_EINVAL, "q_curr, cube_curr, cube_rand, robot_path, cube_path, n_nodes and status are required");
+  if (!model->col.present) return fail(IKG_EINVAL, "%s", model->col.missing);
+  if (model->col.k64.target_geom < 0) return fail(IKG_EINVAL, "the collision scene has no target geometry");
+  ikg::ProjectArgs a{};
+  a.geoms.n = n_geoms;
+  for (int32_t k = 0; k < n_geoms; ++k) {
+    if (geoms[k] < 0 || geoms[k] >= model->col.k64.n_geoms || geoms[k] == model->col.k64.target_geom)
+      return fail(IKG_EINVAL, "geoms[%d] = %d is not a scene geometry other than the target", k, geoms[k]);
+    a.geoms.g[k] = geoms[k];
+  }
+  const int nq = model->desc.nq;
+  if (int rc = check_finite_rows<double>(flags, C, {{q_curr, nq, "q_curr"}, {cube_curr, 12, "cube_curr"}, {cube_rand, 12, "cube_rand"}}))
+    return rc;
+  DeviceGuard g(device);
+  if (g.rc) return g.rc;
+  if (C == 0) return IKG_OK;
+  ikg_model* m = const_cast<ikg_model*>(model);
+  hipStream_t s = (hipStream_t)stream;
+  const ikg::KCollision<double>* dc = nullptr;
+  if (int rc = m->col.get<double>(m->mu, device, &dc)) return rc;
+  // steps to enqueue: every chain ends within max_nodes - 1 steps; a host-pointer
+  // call knows the longest chain (one spare step against a last-bit difference
+  // of the device's own count; a finished chain's extra step changes nothing)
+  int64_t n_steps = (int64_t)max_nodes - 1;
+  if (flags & IKG_FLAG_HOST_POINTERS) {
+    int64_t longest = 0;
+    for (int64_t c = 0; c < C; ++c) {
+      const double *pa = (const double*)cube_curr + 12 * c + 9, *pb = (const double*)cube_rand + 12 * c + 9;
+      if (!(std::sqrt((pa[0] - pb[0]) * (pa[0] - pb[0]) + (pa[1] - pb[1]) * (pa[1] - pb[1]) +
+                      (pa[2] - pb[2]) * (pa[2] - pb[2])) / step_size < 1e9))
+        return fail(IKG_EINVAL, "chain %lld: |dt| / step_size is too large", (long long)c);
+      longest = std::max<int64_t>(longest, (int64_t)ikg::projection_steps(pa, pb, step_size * (1.0 - 1e-12)));
+    }
+    n_steps = std::min(n_steps, longest);
+  }
+  Staging st(s, flags);
+  a.q_curr = (const double*)st.in(q_curr, sizeof(double) * nq * C);
+  a.cube_curr = (const double*)st.in(cube_curr, sizeof(double) * 12 * C);
+  a.cube_rand = (const double*)st.in(cube_rand, sizeof(double) * 12 * C);
+  a.C = C;
+  a.nq = nq;
+  a.max_nodes = max_nodes;
+  a.step_size = step_size;
+  a.robot_path = (double*)st.out(robot_path, sizeof(double) * nq * max_nodes * C);
+  a.cube_path = (double*)st.out(cube_path, sizeof(double) * 12 * max_nodes * C);
+  a.n_nodes = (int32_t*)st.out(n_nodes, sizeof(int32_t) * C);
+  a.status = (int32_t*)st.out(status, sizeof(int32_t) * C);
+  if (st.rc) return st.rc;
+  const ikg::ProjectLayout l(C, nq);
+  ikg::Workspace ws(&m->ws, s, "project");
+  hipError_t e = ws.alloc(l);
+  if (e != hipSuccess) return fail(IKG_ENOMEM, "projection workspace allocation: %s", hipGetErrorString(e));
+  a.targets = ws.at<double>(l.targets);
+  a.q0 = ws.at<double>(l.q0);
+  double* q = ws.at<double>(l.q);
+  uint8_t* conv = ws.at<uint8_t>(l.conv);
+  a.q = q;
+  a.conv = conv;
+  a.steps = ws.at<int32_t>(l.aux);
+  a.free_ = a.steps + C;
+  if (st.host) {  // rows past a chain's end are copied back too: defined, zero
+    e = hipMemsetAsync(a.robot_path, 0, sizeof(double) * nq * max_nodes * C, s);
+    if (e == hipSuccess) e = hipMemsetAsync(a.cube_path, 0, sizeof(double) * 12 * max_nodes * C, s);
+    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(paths)");
+  }
+  // step 1's prepare also writes row 0, the step counts and the states
+  for (int64_t step = 1; step <= std::max<int64_t>(n_steps, 1); ++step) {
+    e = ikg::launch_project_prepare(dc, a, (int)step, s);
+    if (e != hipSuccess) return hip_fail(e, "ikg projection prepare kernel launch");
+    if (step > n_steps) break;  // max_nodes = 1: the chains are cut at their first row
+    if (int rc = solve_batch_t<double>(m, device, a.targets, a.q0, nq, C, params, q, conv, ws.at<int32_t>(l.iters),
+                                       ws.at<double>(l.err), s, 0))
+      return rc;
+    e = ikg::launch_project_commit(a, (int)step, s);
+    if (e != hipSuccess) return hip_fail(e, "ikg projection commit kernel launch");
+  }
+  e = ws.release();
+  if (e != hipSuccess) return hip_fail(e, "projection workspace free");
   return st.finish();
 }
 

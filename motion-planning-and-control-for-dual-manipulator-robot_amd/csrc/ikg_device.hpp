@@ -615,7 +615,12 @@ IKG_HD inline void column(const T* R, int axis, T* a) {
 // which removes three transcendental calls and three divisions from the
 // reference formulas (alpha = theta sin/(2(1-cos)) = theta (1+cos)/(2 sin),
 // beta = 1/theta^2 - sin/(2 theta (1-cos)) = (1-alpha)/theta^2).
-template <typename T>
+// kRefRatio (SE3.Interpolate, ikg_planner.hpp): theta/sin(theta) with the sine
+// of the acos angle itself, as Pinocchio forms it.  Between precision<3>() and
+// about 1e-2 rad acos((tr - 1)/2) carries a relative error of eps/theta^2 (up
+// to 1e-8), which cancels in theta/sin(theta) but not in theta/(|skew|/2); an
+// interpolated placement needs the former.  The default stays as it was.
+template <typename T, bool kRefRatio = false>
 IKG_HD inline void log6(const T* R, const T* p, T* e) {
   const T pi = Prec<T>::kPi;
   const T tr = R[0] + R[4] + R[8];
@@ -643,7 +648,10 @@ IKG_HD inline void log6(const T* R, const T* p, T* e) {
   } else {
     T f;
     if (theta > Prec<T>::kPrec3) {
-      f = fdiv(theta, st);
+      if constexpr (kRefRatio)
+        f = theta / sin(theta);
+      else
+        f = fdiv(theta, st);
     } else if constexpr (sizeof(T) == 8) {
       f = T(1);  // Pinocchio: theta/sin(theta) -> 1 below precision<3>()
     } else {

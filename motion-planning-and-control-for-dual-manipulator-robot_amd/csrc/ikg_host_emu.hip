@@ -16,6 +16,7 @@
 #include "ikg_dynamics.hpp"
 #include "ikg_fit.hpp"
 #include "ikg_model_build.hpp"
+#include "ikg_planner.hpp"
 #include "ikgrasp.h"
 
 namespace {
@@ -810,6 +811,53 @@ extern "C" int ikg_emu_bezier_fit(const double* q0, const double* q1, const doub
     cost[p] = ikg::bezier_fit_path(f, w, ex, points + p * (d + 1) * dim, vpoints ? vpoints + p * d * dim : nullptr,
                                    apoints ? apoints + p * (d - 1) * dim : nullptr);
     status[p] = 0;
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------- planner primitives on the CPU
+// ikg_se3_interpolate_batch with host pointers: the kernel's se3_interpolate (tests/test_rrt.py)
+extern "C" int ikg_emu_se3_interpolate(const double* A, const double* B, const double* alpha, int64_t C, double* out) {
+  for (int64_t i = 0; i < C; ++i) ikg::se3_interpolate(A + 12 * i, B + 12 * i, alpha[i], out + 12 * i);
+  return 0;
+}
+
+// ikg_nearest_batch with host pointers: the kernel's per-row distance and its
+// argmin rule, combined in the kernel's order (64 lanes striding the rows, then
+// the butterfly over the lanes); -1 where the entry returns IKG_EINVAL
+extern "C" int ikg_emu_nearest(const double* nodes, int64_t cap, const int32_t* counts, const double* queries,
+                               int32_t nq, int64_t P, int32_t* index, double* dist) {
+  if (cap < 0 || nq < 1) return -1;
+  for (int64_t p = 0; p < P; ++p) {
+    if (counts[p] < 0 || counts[p] > cap) return -1;
+    double d2[64];
+    int best[64];
+    for (int lane = 0; lane < 64; ++lane) {
+      d2[lane] = DBL_MAX;
+      best[lane] = -1;
+      for (int64_t r = lane; r < counts[p]; r += 64) {
+        const double d = ikg::row_dist2(nodes + (p * cap + r) * nq, queries + p * nq, nq);
+        if (ikg::nearest_takes(d2[lane], best[lane], d, (int)r)) {
+          d2[lane] = d;
+          best[lane] = (int)r;
+        }
+      }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      double od[64];
+      int ob[64];
+      for (int lane = 0; lane < 64; ++lane) {
+        od[lane] = d2[lane ^ off];
+        ob[lane] = best[lane ^ off];
+      }
+      for (int lane = 0; lane < 64; ++lane)
+        if (ikg::nearest_takes(d2[lane], best[lane], od[lane], ob[lane])) {
+          d2[lane] = od[lane];
+          best[lane] = ob[lane];
+        }
+    }
+    index[p] = best[0];
+    dist[p] = best[0] >= 0 ? std::sqrt(d2[0]) : 0.0;
   }
   return 0;
 }

@@ -146,6 +146,7 @@ EXPORTS = [
     "ikg_model_set_inertia", "ikg_dynamics_batch", "ikg_control_params_default", "ikg_control_torque_batch",
     "ikg_forward_dynamics_batch", "ikg_bezier_eval_batch", "ikg_rollout_params_default", "ikg_control_rollout",
     "ikg_control_rollout_curves", "ikg_fit_params_default", "ikg_bezier_fit_batch",
+    "ikg_se3_interpolate_batch", "ikg_nearest_batch", "ikg_project_paths",
 ]
 
 _lib = None
@@ -236,6 +237,13 @@ def load() -> C.CDLL:
     lib.ikg_bezier_fit_batch.argtypes = [i32, vp, vp, vp, vp, i64, C.c_int32, C.POINTER(FitParams), vp, vp, vp, vp, vp,
                                          vp, C.c_uint32]
     lib.ikg_bezier_fit_batch.restype = i32
+    lib.ikg_se3_interpolate_batch.argtypes = [i32, vp, vp, vp, i64, vp, vp, C.c_uint32]
+    lib.ikg_se3_interpolate_batch.restype = i32
+    lib.ikg_nearest_batch.argtypes = [i32, vp, i64, vp, vp, C.c_int32, i64, vp, vp, vp, C.c_uint32]
+    lib.ikg_nearest_batch.restype = i32
+    lib.ikg_project_paths.argtypes = [vp, i32, vp, vp, vp, i64, C.c_double, C.c_int32, vp, C.c_int32,
+                                      C.POINTER(Params), vp, vp, vp, vp, vp, C.c_uint32]
+    lib.ikg_project_paths.restype = i32
     lib.ikg_model_specialize.argtypes = [vp, i32, i32, C.c_uint32]
     lib.ikg_model_specialize.restype = i32
     lib.ikg_model_is_specialized.argtypes = [vp, i32, i32]

@@ -321,6 +321,76 @@ class IKSolver:
                                                  _lib.IKG_FLAG_HOST_POINTERS))
         return out.astype(bool)
 
+    # ------------------------------------------------------------------ RRT-Connect planner primitives (fp64)
+    def _i32_io(self, first):
+        """(prep, empty) for int32 arrays of `first`'s kind (numpy, or tensors on its device)."""
+        if _is_torch(first):
+            import torch
+            return (lambda x: x.to(device=first.device, dtype=torch.int32).contiguous().view(-1),
+                    lambda *shape: torch.empty(shape, dtype=torch.int32, device=first.device))
+        return (lambda x: np.ascontiguousarray(x, dtype=np.int32).reshape(-1),
+                lambda *shape: np.empty(shape, dtype=np.int32))
+
+    def se3_interpolate(self, A, B, alpha, stream=None):
+        """ikg_se3_interpolate_batch: pin.SE3.Interpolate(A[c], B[c], alpha[c]) ->
+        [C,12].  A, B [C,12], alpha [C] (numpy, or float64 ROCm tensors)."""
+        prep, empty, ptr, s, device, flags = self._f64_io(A, stream)
+        aa, bb, al = prep(A, 12), prep(B, 12), prep(alpha, 1)
+        n = aa.shape[0]
+        if bb.shape[0] != n or al.shape[0] != n:
+            raise ValueError(f"A has {n} rows: B and alpha need as many")
+        out = empty(n, 12)
+        _lib.check(self.lib.ikg_se3_interpolate_batch(device, ptr(aa), ptr(bb), ptr(al), n, ptr(out), s, flags))
+        return out
+
+    def nearest(self, nodes, counts, queries, stream=None):
+        """ikg_nearest_batch: per tree the nearest row to its query, the lowest
+        index among exact ties -> (index [P] int32, dist [P]).  nodes
+        [P,cap,nq] (any row length nq), counts [P], queries [P,nq] (numpy, or
+        ROCm tensors: float64 and int32); counts[p] == 0 gives index -1."""
+        if nodes.ndim != 3:
+            raise ValueError(f"nodes must be [P, cap, nq], got {list(nodes.shape)}")
+        P, cap, nq = (int(x) for x in nodes.shape)
+        prep, empty, ptr, s, device, flags = self._f64_io(nodes, stream)
+        iprep, iempty = self._i32_io(nodes)
+        nn, qq, cc = prep(nodes, nq), prep(queries, nq), iprep(counts)
+        if qq.shape[0] != P or cc.shape[0] != P:
+            raise ValueError(f"nodes hold {P} trees: queries and counts need as many rows")
+        index, dist = iempty(P), empty(P)
+        _lib.check(self.lib.ikg_nearest_batch(device, ptr(nn), cap, ptr(cc), ptr(qq), nq, P, ptr(index), ptr(dist), s,
+                                              flags))
+        return index, dist
+
+    def project_paths(self, q_curr, cube_curr, cube_rand, step_size=0.025, max_nodes=64, geoms=None, stream=None,
+                      **kw) -> dict:
+        """ikg_project_paths: path.py:125-163 for C chains, the whole loop on
+        the device.  q_curr [C,nq], cube_curr, cube_rand [C,12] (numpy, or
+        float64 ROCm tensors: then nothing waits on the host).  geoms: the
+        world-fixed geometries of the placement check (default: the scene's
+        table and obstacle).  `kw`: the solve's parameters (default: the
+        planner's check_collision=True).  -> dict of robot_path
+        [C,max_nodes,nq], cube_path [C,max_nodes,12], n_nodes [C], status [C]
+        (0 reached, 1 placement collision, 2 failed IK, 3 cut at max_nodes)."""
+        if self.scene is None:
+            raise RuntimeError("project_paths needs a collision scene (set_collision)")
+        kw.setdefault("check_collision", True)
+        prm = self.params(**kw)
+        nq = self.nq
+        prep, empty, ptr, s, device, flags = self._f64_io(q_curr, stream)
+        _, iempty = self._i32_io(q_curr)
+        qq, ca, cb = prep(q_curr, nq), prep(cube_curr, 12), prep(cube_rand, 12)
+        n = qq.shape[0]
+        if ca.shape[0] != n or cb.shape[0] != n:
+            raise ValueError(f"q_curr has {n} rows: cube_curr and cube_rand need as many")
+        g = np.ascontiguousarray(self.scene.env_geoms() if geoms is None else geoms, dtype=np.int32).reshape(-1)
+        M = int(max_nodes)
+        res = {"robot_path": empty(n, M, nq), "cube_path": empty(n, M, 12), "n_nodes": iempty(n), "status": iempty(n)}
+        self._auto_specialize(device, _lib.IKG_F64)
+        _lib.check(self.lib.ikg_project_paths(self._h, device, ptr(qq), ptr(ca), ptr(cb), n, float(step_size), M,
+                                              g.ctypes.data, g.size, C.byref(prm), ptr(res["robot_path"]),
+                                              ptr(res["cube_path"]), ptr(res["n_nodes"]), ptr(res["status"]), s, flags))
+        return res
+
     # ------------------------------------------------------------------ log6
     def log6(self, M, dtype="f64") -> np.ndarray:
         """pin.log6 of placements [B,12] -> [B,6] ([v; w])."""
