@@ -479,6 +479,82 @@ extern "C" int ikg_emu_math(int fn, int64_t n, const double* x, const double* y,
   return 0;
 }
 
+// The SE(3) log / exp evaluators over arrays, in the instantiations the kernels
+// use (tests/test_se3.py).  M [n,12] = R row-major, then p; out [n,6] = [v; w]
+// ([n,12] for exp6, whose xi = M[12 i .. 12 i + 6)).
+//   fn 0: log6<double> (ikg_log6_batch f64, the controller's err)
+//      1: log6<float> (ikg_log6_batch f32; inputs cast)
+//      2: log6<double, true> (SE3.Interpolate)        3: exp6<double>
+//      4: log6_iter<double>, no tracker
+//      5: log6_iter<double> (quad loop)                6: log6_iter<double, true> (pair loop)
+//      7: log6_iter<double, true, true> (pair loop, z-aligned targets: its sums uncontracted)
+//         5-7 with a tracker.  prev == NULL: a resync update (the tracker zero-initialised, as
+//         update 0 finds it).  prev [n,12]: the tracker filled by a resync update on prev[i],
+//         then M[i] with resync = false.  fn + 10 (15-17): the rows are ONE chain: a resync
+//         update on prev[0 .. 12), then M[0], M[1], ... in turn with resync = false.
+//      8: log6_iter<float, true> (pair fp32 loop)
+//      9: log6_iter<v2f> (packed loop), both halves fed the row: -2 if they differ
+template <bool COLD, bool ROW3>
+static void emu_se3_tracked(bool chain, int64_t n, const double* M, const double* prev, double* out) {
+  using namespace ikg;
+  ThetaTrack<double> tk{};
+  double e[6];
+  for (int64_t i = 0; i < n; ++i) {
+    if (prev && (!chain || i == 0)) {
+      tk = ThetaTrack<double>{};
+      log6_iter<double, COLD, ROW3>(prev + 12 * i, prev + 12 * i + 9, e, &tk, true);
+    } else if (!prev) {
+      tk = ThetaTrack<double>{};
+    }
+    log6_iter<double, COLD, ROW3>(M + 12 * i, M + 12 * i + 9, out + 6 * i, &tk, prev == nullptr);
+  }
+}
+
+extern "C" int ikg_emu_se3(int fn, int64_t n, const double* M, const double* prev, double* out) {
+  using namespace ikg;
+  const bool chain = fn >= 15 && fn <= 17;
+  if (chain && !prev) return -1;
+  switch (chain ? fn - 10 : fn) {
+    case 5: emu_se3_tracked<false, false>(chain, n, M, prev, out); return 0;
+    case 6: emu_se3_tracked<true, false>(chain, n, M, prev, out); return 0;
+    case 7: emu_se3_tracked<true, true>(chain, n, M, prev, out); return 0;
+    default: break;
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    const double* Mi = M + 12 * i;
+    double* o = out + 6 * i;
+    float Mf[12], ef[6];
+    for (int k = 0; k < 12; ++k) Mf[k] = (float)Mi[k];
+    switch (fn) {
+      case 0: log6<double>(Mi, Mi + 9, o); break;
+      case 1:
+        log6<float>(Mf, Mf + 9, ef);
+        for (int k = 0; k < 6; ++k) o[k] = ef[k];
+        break;
+      case 2: log6<double, true>(Mi, Mi + 9, o); break;
+      case 3: exp6<double>(Mi, out + 12 * i, out + 12 * i + 9); break;
+      case 4: log6_iter<double>(Mi, Mi + 9, o); break;
+      case 8:
+        log6_iter<float, true>(Mf, Mf + 9, ef);
+        for (int k = 0; k < 6; ++k) o[k] = ef[k];
+        break;
+      case 9: {
+        v2f Mv[12], ev[6];
+        for (int k = 0; k < 12; ++k) Mv[k] = v2f{Mf[k], Mf[k]};
+        log6_iter<v2f>(Mv, Mv + 9, ev);
+        for (int k = 0; k < 6; ++k) {
+          const float a = ev[k].x, b = ev[k].y;
+          if (std::memcmp(&a, &b, sizeof(float)) != 0) return -2;
+          o[k] = a;
+        }
+        break;
+      }
+      default: return -1;
+    }
+  }
+  return 0;
+}
+
 // What every dynamics entry below starts with: the inertias pass
 // ikg_model_set_inertia's checks (else null) and the joint and inertia tables
 // are built into this thread's storage.

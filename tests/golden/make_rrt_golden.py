@@ -116,42 +116,11 @@ def _pack(prefix, r, out):
     out[f"{prefix}_next"] = np.array(r["next"])
 
 
-# ---------------------------------------------------------------- SE3.Interpolate in 50 digits
-def _mp_interpolate(A, B, alpha):
-    import mpmath as mp
-    mp.mp.dps = 50
-    Ra, ta = mp.matrix(A[0].tolist()), mp.matrix(A[1].tolist())
-    Rb, tb = mp.matrix(B[0].tolist()), mp.matrix(B[1].tolist())
-    R = Ra.T * Rb
-    p = Ra.T * (tb - ta)
-    skew = mp.matrix([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
-    st = mp.sqrt(sum(x * x for x in skew)) / 2
-    theta = mp.atan2(st, (R[0, 0] + R[1, 1] + R[2, 2] - 1) / 2)
-    if theta == 0:
-        w, v = mp.matrix([0, 0, 0]), p
-    else:
-        w = skew * (theta / (2 * st))
-        s, c = mp.sin(theta), mp.cos(theta)
-        al = theta * s / (2 * (1 - c))
-        be = 1 / theta ** 2 - s / (2 * theta * (1 - c))
-        wxp = mp.matrix([w[1] * p[2] - w[2] * p[1], w[2] * p[0] - w[0] * p[2], w[0] * p[1] - w[1] * p[0]])
-        v = al * p - wxp / 2 + (be * (w.T * p)[0]) * w
-    w, v = alpha * w, alpha * v
-    t = mp.sqrt(sum(x * x for x in w))
-    W = mp.matrix([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
-    if t == 0:
-        Re, te = mp.eye(3), v
-    else:
-        a, b, c = mp.sin(t) / t, (1 - mp.cos(t)) / t ** 2, (t - mp.sin(t)) / t ** 3
-        Re = mp.eye(3) + a * W + b * (W * W)
-        te = (mp.eye(3) + b * W + c * (W * W)) * v
-    Ro, to = Ra * Re, ta + Ra * te
-    return np.array([float(Ro[i, j]) for i in range(3) for j in range(3)] + [float(to[i]) for i in range(3)])
-
-
+# ---------------------------------------------------------------- SE3.Interpolate in 50 digits (tests/se3_oracle.py)
 def make_interp(out):
     from scipy.spatial.transform import Rotation
     from oracle import planner_oracle as po
+    from se3_oracle import interpolate_mp
     rng = np.random.default_rng(31)
     rows = []
     for k, ang in enumerate(ANGLES):
@@ -164,7 +133,7 @@ def make_interp(out):
         for al in ALPHAS:
             R, t = po.se3_interpolate(A, B, al)
             f64 = np.concatenate([R.reshape(9), t])
-            exact = _mp_interpolate(A, B, al)
+            exact = interpolate_mp(A, B, al)
             rows.append((ang, al, np.concatenate([Ra.reshape(9), ta]), np.concatenate([Rb.reshape(9), B[1]]), f64,
                          exact, np.abs(f64 - exact).max()))
     for i, name in enumerate(("angle", "alpha", "A", "B", "oracle", "exact", "err")):
