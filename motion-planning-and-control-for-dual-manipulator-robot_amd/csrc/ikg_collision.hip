@@ -80,9 +80,6 @@ __device__ unsigned long long g_wprof[6];
 // wave-wide rounds of 64 with an early exit on the first round holding a hit,
 // whose lowest pair becomes the new witness.  The result is the OR over all
 // active pairs either way: only the order of the tests changes.
-#ifndef IKG_SWEEP_COMPACT
-#define IKG_SWEEP_COMPACT 1
-#endif
 template <typename T, bool WITNESS>
 __device__ bool collide_wave(const KModel<T>* __restrict__ m, const KCollision<T>* __restrict__ c,
                              CollideScratch<T>& S, const T* tgt, Witness<T>& W,
@@ -132,7 +129,6 @@ __device__ bool collide_wave(const KModel<T>* __restrict__ m, const KCollision<T
   for (int g = lane; g < c->n_geoms; g += 64) geom_world(c, g, S.F, tgt, S.P[g]);
   __syncthreads();
   bool found = false;
-#if IKG_SWEEP_COMPACT
   // Two passes: the bounding-sphere test of every pair, the survivors listed
   // in pair order (ballot + popcount), then the exact tests over the list in
   // rounds of 64.  A collision-free pose runs ~2 narrow-phase rounds instead of
@@ -192,18 +188,6 @@ __device__ bool collide_wave(const KModel<T>* __restrict__ m, const KCollision<T
       break;
     }
   }
-#else
-  for (int base = 0; base < c->n_pairs; base += 64) {
-    const int k = base + lane;
-    const bool hit = k < c->n_pairs && k != w && pair_hit(c, k, S.P) != 0;
-    const unsigned long long bal = __ballot(hit);
-    if (bal) {
-      if (WITNESS && lane == 0) W.pair = base + __ffsll((long long)bal) - 1;
-      found = true;
-      break;
-    }
-  }
-#endif
   if (WITNESS && lane == 0) {
     if (!found) W.pair = -1;
     W.cert_ok = 0;
@@ -743,7 +727,7 @@ __device__ __forceinline__ T cont_step(const KModel<T>* __restrict__ m, const KP
   T x;
   if constexpr (FRAMES)
     x = arm_fk_error<T, SP, true>(m, arm, sn, cs, RT, tT, st, F);
-  else if constexpr (IKG_THETA_TRACK && is_f64<T>)
+  else if constexpr (is_f64<T>)
     x = arm_fk_error<T, SP>(m, arm, sn, cs, RT, tT, st, nullptr, tk, resync);
   else
     x = arm_fk_error<T, SP>(m, arm, sn, cs, RT, tT, st);
@@ -800,7 +784,7 @@ __device__ __forceinline__ T stretch_step(const KModel<T>* __restrict__ m, const
                                           ThetaTrack<T>* tk, bool resync) {
   if constexpr (kStretchF1<SP, DAMPED>) {
     ArmStateF1<T> st;
-    const T x = arm_fk_error_f1<T, SP>(m, arm, sn, cs, RT, tT, st, (IKG_THETA_TRACK && is_f64<T>) ? tk : nullptr,
+    const T x = arm_fk_error_f1<T, SP>(m, arm, sn, cs, RT, tT, st, is_f64<T> ? tk : nullptr,
                                        resync);
     pinv_step_f1<T, SP>(m, arm, st, sn, cs, dq, s);
     return x;
@@ -2156,11 +2140,9 @@ void ikg_traj_update_kernel(const KModel<T>* __restrict__ m, KParams<T> prm,
 // check at the batch kernel's iterate and the window boxes (window_covers);
 // with witness0, over the pre-screen's colliding list (clist, *count): the
 // window boxes only
-#ifndef IKG_FC_WAVES64  // timing knob: waves per SIMD the fp64 first check and records scan are compiled for
-#define IKG_FC_WAVES64 1
-#endif
+constexpr int kFcWaves64 = 1;  // waves per SIMD the fp64 first check and records scan are compiled for
 template <typename T>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 ? 3 : IKG_FC_WAVES64)))
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 ? 3 : kFcWaves64)))
 void ikg_first_check_kernel(const KModel<T>* __restrict__ m, const KCollision<T>* __restrict__ c,
                             const T* __restrict__ targets, int64_t S_per_target, int64_t B,
                             const int32_t* __restrict__ clist, const int32_t* __restrict__ count,
@@ -2173,7 +2155,7 @@ void ikg_first_check_kernel(const KModel<T>* __restrict__ m, const KCollision<T>
 // fp32: at most 168 VGPRs, so 3 waves fit a SIMD as before the certificate
 // code (which alone would take the kernel to 182 and 2 waves)
 template <typename T>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 ? 3 : IKG_FC_WAVES64)))
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 ? 3 : kFcWaves64)))
 void ikg_traj_scan_kernel(const KModel<T>* __restrict__ m,
                                                            const KCollision<T>* __restrict__ c,
                                                            const T* __restrict__ targets, int64_t S_per_target,

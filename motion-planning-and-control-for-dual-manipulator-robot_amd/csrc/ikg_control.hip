@@ -34,10 +34,7 @@ namespace ikg {
 
 namespace {
 
-#ifndef IKG_FK_TILE
-#define IKG_FK_TILE 32
-#endif
-constexpr int kStatesPerTile = IKG_FK_TILE;
+constexpr int kStatesPerTile = 32;
 // LDS holds the dense matrices of one slice of the tile at a time and the
 // emission pass runs once per slice.  fp64: two slices of 16 states (23 KB,
 // 6 workgroups per CU instead of 3) -- measured -18% for the task_space_terms

@@ -18,45 +18,7 @@
 // exact kernel arithmetic on the CPU for debugging (never a product path).
 #define IKG_HD __host__ __device__
 
-// Timing-only ablation switches (tools/ablate.py builds; never the shipped
-// library): bit 0 = cheap joint sincos, bit 1 = trivial log6,
-// bit 2 = skip the 6x6 solve.
-#ifndef IKG_ABL
-#define IKG_ABL 0
-#endif
-// rotation angle in the loop's log6 (fp64): 0 = acos((tr R - 1)/2) as pin.log3,
-// 1 = atan2(|skew|/2, (tr R - 1)/2)
-#ifndef IKG_THETA
-#define IKG_THETA 0
-#endif
-// log6's small-angle series by multiplications instead of divisions
-#ifndef IKG_TAYLOR_MUL
-#define IKG_TAYLOR_MUL 1
-#endif
-// fp64 log6 in the loop: Pinocchio's small-angle series for alpha, beta below
-// precision<3>() (1) or the closed forms throughout (0)
-#ifndef IKG_LOG6_SERIES
-#define IKG_LOG6_SERIES 1
-#endif
-// pair kernel: per-lane joint limits held in registers (12 fp64) instead of
-// clamping against both arms' scalar limits and selecting
-#ifndef IKG_LANE_LIMITS
-#define IKG_LANE_LIMITS 1
-#endif
-// Nextage-pattern models: iterate in the frame of the first arm joint with the
-// closed-form arm solve (arm_fk_error_f1 / arm_solve_f1) instead of the chest
-// frame and the two 3x3 Cramer solves
-#ifndef IKG_FRAME1
-#define IKG_FRAME1 1
-#endif
-// carry the rotation angle across iterations (ThetaTrack)
-#ifndef IKG_THETA_TRACK
-#define IKG_THETA_TRACK 1
-#endif
-// angle increment by a division-free asin series (1) or atan(y/x) (0)
-#ifndef IKG_THETA_ASIN
-#define IKG_THETA_ASIN 1
-#endif
+namespace ikg {
 
 // The singularity guard of the closed-form step (pinv_step_*).  The closed
 // form dq_a = u_a - s v_a (v_a = J_a^-1 c_a, s ~ |u| / |v|) rounds to
@@ -76,25 +38,12 @@
 // bounds trip on unconverged problems that wander near the wrist for
 // hundreds of updates (C5-style random seeds: 630 of 505,859 fp64 updates at
 // 1e10, 17 at 1e14), stalling their waves.
-// Timing knob: IKG_SING_GUARD=0 builds the unguarded closed form.
-#ifndef IKG_SING_GUARD
-#define IKG_SING_GUARD 1
-#endif
-#ifndef IKG_SING_BETA64
-#define IKG_SING_BETA64 1e14
-#endif
-#ifndef IKG_SING_BETA32
-#define IKG_SING_BETA32 1e12f
-#endif
+// (a model can carry other bounds: ikg_model_build.hpp)
+constexpr double kSingBeta64 = 1e14;
+constexpr float kSingBeta32 = 1e12f;
 // generic-path (chest frame, Householder / 3 x 3 adjugate) relative pivot bound
-#ifndef IKG_SING_TAU64
-#define IKG_SING_TAU64 1e-7
-#endif
-#ifndef IKG_SING_TAU32
-#define IKG_SING_TAU32 1e-4
-#endif
-
-namespace ikg {
+constexpr double kSingTau64 = 1e-7;
+constexpr float kSingTau32 = 1e-4f;
 
 constexpr int kArmDof = 6;
 constexpr int kMaxNq = 32;
@@ -213,19 +162,16 @@ IKG_HD inline bool any_of(bool m) { return m; }
 IKG_HD inline bool any_of(v2i m) { return m.x != 0 || m.y != 0; }
 IKG_HD inline bool all_of(bool m) { return m; }
 IKG_HD inline bool all_of(v2i m) { return m.x != 0 && m.y != 0; }
-// Wave-uniform branch conditions (IKG_UNIFORM): a rare per-lane path (exact
+// Wave-uniform branch conditions: a rare per-lane path (exact
 // trig / acos, the near-pi axis) is run by the whole wave when any lane needs
 // it and its result selected per lane, so the branch is a scalar one -- no
 // EXEC save/restore or phi copies on the common path, and every lane's value
 // is the one it computed before (the selects keep the other lanes' results).
-#ifndef IKG_UNIFORM
-#define IKG_UNIFORM 1
-#endif
 // Not for the packed fp32 layout: there the scalar branches cost 2-3% at C3
 // under its max-ILP schedule (round 3 A/B), so T = v2f keeps per-lane ones.
 template <typename T>
 IKG_HD inline bool wave_any(bool b) {
-#if defined(__HIP_DEVICE_COMPILE__) && IKG_UNIFORM
+#ifdef __HIP_DEVICE_COMPILE__
   if constexpr (!LaneT<T>::packed) return __builtin_amdgcn_ballot_w64(b) != 0;
 #endif
   return b;
@@ -275,17 +221,11 @@ IKG_HD inline v2f atan2f(v2f y, v2f x) { return atan2(y, x); }
 // fp32; ~1 ulp overall).  The reduction stays within ~1e-16 absolute for
 // |x| < 2^40 (fp64; fp32: |x| < 2^16), far beyond any joint angle.  It replaces
 // OCML's sincos, whose Payne-Hanek path for huge arguments is dead weight in
-// the loop's exact trig (every 16th fp32 update: IKG_CW_SINCOS=0 restores it).
-#ifndef IKG_CW_SINCOS
-#define IKG_CW_SINCOS 1
-#endif
-// The packed pair keeps OCML's sincosf (0).  The polynomial in packed math (1)
-// or per half (2) measured 4% slower at C3 (fp32, q = 0; its exact trig runs
-// at resyncs only), and (1) 3% faster with random seeds (large steps)
+// the loop's exact trig (every 16th fp32 update).
+// The packed pair keeps OCML's sincosf.  The polynomial in packed math or per
+// half measured 4% slower at C3 (fp32, q = 0; its exact trig runs at resyncs
+// only), and the packed one 3% faster with random seeds (large steps)
 // (profiles/r02/fp32_math_ab.txt, interleaved A/B of same-flag builds).
-#ifndef IKG_CW_SINCOS_PACKED
-#define IKG_CW_SINCOS_PACKED 0
-#endif
 template <typename T>
 IKG_HD inline void cw_poly(T r, T& sr, T& cr) {
   const T r2 = r * r;
@@ -362,11 +302,7 @@ struct Prec<double> {
   // relative cut-off for the triangular solve (np.linalg.pinv rcond = 1e-15)
   static constexpr double kRcond = 1e-15;
   IKG_HD static inline void sincos_(double x, double* s, double* c) {
-#if IKG_CW_SINCOS
     cw_sincos(x, s, c);
-#else
-    ::sincos(x, s, c);
-#endif
   }
 };
 
@@ -379,11 +315,7 @@ struct Prec<float> {
   static constexpr float kPi = 3.14159265358979323846f;
   static constexpr float kRcond = 1e-7f;
   IKG_HD static inline void sincos_(float x, float* s, float* c) {
-#if IKG_CW_SINCOS
     cw_sincos(x, s, c);
-#else
-    ::sincosf(x, s, c);
-#endif
   }
 };
 
@@ -393,32 +325,11 @@ struct Prec<v2f> {
   static constexpr float kPi = Prec<float>::kPi;
   static constexpr float kRcond = Prec<float>::kRcond;
   IKG_HD static inline void sincos_(v2f x, v2f* s, v2f* c) {
-#if IKG_CW_SINCOS && IKG_CW_SINCOS_PACKED == 1
-    // both halves' reductions and polynomials in packed math, quadrants per half
-    const v2f n = v2f{rintf(x.x * 0.636619772f), rintf(x.y * 0.636619772f)};
-    v2f r = x - n * 1.57079637f;  // contracted: fma(-n, C, x)
-    r = r - n * -4.37113883e-08f;
-    r = r - n * -1.71512489e-15f;
-    v2f sr, cr;
-    cw_poly(r, sr, cr);
-    float s0, c0, s1, c1;
-    cw_quadrant((int)n.x, sr.x, cr.x, &s0, &c0);
-    cw_quadrant((int)n.y, sr.y, cr.y, &s1, &c1);
-    *s = v2f{s0, s1};
-    *c = v2f{c0, c1};
-#elif IKG_CW_SINCOS && IKG_CW_SINCOS_PACKED == 2
-    float s0, c0, s1, c1;  // the scalar polynomial per half
-    cw_sincos(x.x, &s0, &c0);
-    cw_sincos(x.y, &s1, &c1);
-    *s = v2f{s0, s1};
-    *c = v2f{c0, c1};
-#else
     float s0, c0, s1, c1;
     ::sincosf(x.x, &s0, &c0);
     ::sincosf(x.y, &s1, &c1);
     *s = v2f{s0, s1};
     *c = v2f{c0, c1};
-#endif
   }
 };
 
@@ -478,10 +389,7 @@ IKG_HD inline T frcp(T b) {
 
 // sqrt(x) for 0 <= x <= 4 (|skew| of a rotation): OCML's refinement without
 // its denormal scaling and special-value selects (x = 0 gives 0); fp32: the
-// hardware v_sqrt_f32 (IKG_RAW_SQRTF=0: OCML's sqrtf)
-#ifndef IKG_RAW_SQRTF
-#define IKG_RAW_SQRTF 1
-#endif
+// hardware v_sqrt_f32
 template <typename T>
 IKG_HD inline T fsqrt_unit(T x) {
 #ifdef __HIP_DEVICE_COMPILE__
@@ -494,8 +402,6 @@ IKG_HD inline T fsqrt_unit(T x) {
     // one correction already rounds correctly (tools/ubench/rcp.hip)
     const double d = fma(-g, g, x);
     return fma(d, h, g);
-  } else if constexpr (!IKG_RAW_SQRTF) {
-    return sqrt(x);
   } else if constexpr (is_packed<T>) {
     // v_sqrt_f32 (1 ulp) without OCML's denormal scaling and class checks
     return T{__builtin_amdgcn_sqrtf(x.x), __builtin_amdgcn_sqrtf(x.y)};
@@ -694,17 +600,17 @@ IKG_HD inline void log6(const T* R, const T* p, T* e) {
 // branches and formulas), arranged for latency.  In the loop one
 // wave per SIMD runs a single dependent chain FK -> log6 -> solve, so log6's
 // branches (which split the schedule) and its serial sqrt/acos/division chain
-// dominated the iteration (tools/ablate.py IKG_ABL=2: 29% of it).  Here:
+// dominated the iteration (29% of it with log6 ablated).  Here:
 //  * every branch except the rare near-pi axis is a select, so the scheduler can
 //    overlap log6 with the error-independent Jacobian work;
 //  * the near-pi branch needs no sincos: cos(theta - pi) = -cos(theta) and
 //    sin(theta) = |skew|/2 (accurate near pi in absolute terms);
 //  * guarded denominators keep the unselected lanes finite.
 // Rotation angle carried across iterations (log6_iter): the hand moves a little
-// per update, so theta = theta_prev + atan2(sin(theta - theta_prev), cos(...))
-// with the difference angle from (sin, cos) of both (angle subtraction) and a
-// short odd series for its atan; exact acos/atan2 at it % kResync == 0 and
-// whenever |theta - theta_prev| > kInc.
+// per update, so theta = theta_prev + asin(sin(theta - theta_prev))
+// with the difference angle's sine from (sin, cos) of both (angle subtraction) and a
+// short division-free series for its asin; exact acos at it % kResync == 0 and
+// whenever |sin(theta - theta_prev)| > kIncAsin.
 template <typename T>
 struct ThetaTrack {
   T th, st, ct;
@@ -713,11 +619,6 @@ template <typename T>
 struct ThetaInc;
 template <>
 struct ThetaInc<double> {
-  static constexpr double kInc = 0.05;  // r^13/13 < 1e-17 r
-  IKG_HD static inline double atan_small(double r) {
-    const double r2 = r * r;
-    return r + r * r2 * (-1.0 / 3 + r2 * (1.0 / 5 + r2 * (-1.0 / 7 + r2 * (1.0 / 9 + r2 * (-1.0 / 11)))));
-  }
   // |y| <= 0.035 (the angle moves ~1% of itself per update): the first dropped
   // term 63/2816 y^11 < 3e-18
   static constexpr double kIncAsin = 0.035;
@@ -728,11 +629,6 @@ struct ThetaInc<double> {
 };
 template <>
 struct ThetaInc<float> {
-  static constexpr float kInc = 0.05f;
-  IKG_HD static inline float atan_small(float r) {
-    const float r2 = r * r;
-    return r + r * r2 * (-1.0f / 3 + r2 * (1.0f / 5 + r2 * (-1.0f / 7)));
-  }
   static constexpr float kIncAsin = 0.035f;
   IKG_HD static inline float asin_small(float y) {
     const float y2 = y * y;
@@ -745,9 +641,6 @@ struct ThetaInc<float> {
 // for atan(a) (fit here, max error 5.3e-8 abs evaluated in fp32, ~0.9 ulp at
 // pi/4), then pi/2 - . and pi - . by selects -- all packed math for v2f,
 // where OCML's atan2f ran once per half with its special-case handling.
-#ifndef IKG_FAST_ATAN2
-#define IKG_FAST_ATAN2 1
-#endif
 template <typename T>
 IKG_HD inline T atan2_upper(T y, T x) {
   const T ax = fabs(x);
@@ -823,23 +716,14 @@ IKG_HD inline void log6_iter(const T* R, const T* p, T* e, ThetaTrack<T>* tk = n
     if (tk && (COLD || !resync)) {
       const T y = st * tk->ct - ct * tk->st;  // rho sin(theta - theta_prev)
       const T x = ct * tk->ct + st * tk->st;  // rho cos(theta - theta_prev)
-#if IKG_THETA_ASIN
       // rho = |(st, ct)| |(st', ct')| = 1 up to the rotations' rounding (~1e-15),
       // so delta = asin(y) to that relative accuracy: a division-free series
       exact = !(fabs(y) <= ThetaInc<T>::kIncAsin && x > T(0));
       theta = tk->th + ThetaInc<T>::asin_small(y);
-#else
-      exact = !(fabs(y) <= ThetaInc<T>::kInc * x);
-      theta = tk->th + ThetaInc<T>::atan_small(fdiv<T>(y, fmax(x, T(1e-30))));
-#endif
       if constexpr (COLD) exact = exact || resync;
     }
     if (IKG_RARELY(COLD, wave_any<T>(exact))) {
-#if IKG_THETA == 1
-      const T th_x = atan2(st, ct);
-#else
       const T th_x = acos(fmin(fmax(ct, T(-1)), T(1)));  // pin.log3: tr > 3 -> 0, tr < -1 -> pi
-#endif
       theta = exact ? th_x : theta;
     }
     if (tk) {
@@ -848,11 +732,7 @@ IKG_HD inline void log6_iter(const T* R, const T* p, T* e, ThetaTrack<T>* tk = n
       tk->ct = ct;
     }
   } else {
-#if IKG_FAST_ATAN2
     theta = atan2_upper(st, ct);  // fp32: accurate near 0 where acos is not
-#else
-    theta = atan2f(st, ct);
-#endif
   }
   const T t2 = theta * theta;
   const T tiny = is_f64<T> ? T(1e-300) : T(1e-30f);
@@ -885,26 +765,13 @@ IKG_HD inline void log6_iter(const T* R, const T* p, T* e, ThetaTrack<T>* tk = n
   }
   T beta;
   if constexpr (is_f64<T>) {
-#if IKG_LOG6_SERIES
-#if IKG_TAYLOR_MUL
     // Pinocchio's series terms t2/12, t2^2/720 as products with the rounded
     // reciprocals (<= 1 ulp of each term; the branch serves theta < 1.2e-4):
     // three IEEE divisions (~11 instructions each) leave the loop
     const T as = T(1) - t2 * T(1.0 / 12) - (t2 * t2) * T(1.0 / 720);
     const T bs = T(1.0 / 12) + t2 * T(1.0 / 720);
-#else
-    const T as = T(1) - t2 / T(12) - t2 * t2 / T(720);
-    const T bs = T(1) / T(12) + t2 / T(720);
-#endif
     beta = vsel<T>(below, bs, (T(1) - alpha) * inv_t2);
     alpha = vsel<T>(below, as, alpha);
-#else
-    // no series branch: theta (1 + cos)/(2 sin) has no cancellation at small
-    // theta, and (1 - alpha)/theta^2's cancellation error (eps/theta^2) reaches
-    // v only through beta (w.p) w with |w|^2 = theta^2: ~eps |p| absolute
-    (void)below;
-    beta = (T(1) - alpha) * inv_t2;
-#endif
   } else {
     const T as = T(1) - t2 * (T(1.f / 12) + t2 * (T(1.f / 720) + t2 * T(1.f / 30240)));
     const T bs = T(1.f / 12) + t2 * (T(1.f / 720) + t2 * (T(1.f / 30240) + t2 * T(1.f / 1209600)));
@@ -931,9 +798,6 @@ IKG_HD inline void log6_iter(const T* R, const T* p, T* e, ThetaTrack<T>* tk = n
 // iteration of pin.framesForwardKinematics (inverse_geometry.py:58).
 template <typename T>
 struct Trig;
-#ifndef IKG_RESYNC64
-#define IKG_RESYNC64 128
-#endif
 // the chest-frame path's trig rule (generic models, the damped solve, the
 // collision continuation's chest-frame loop): 2 = the longer series for every
 // step up to kIncMed (the tilted robot's trajectories take steps beyond the
@@ -950,7 +814,7 @@ struct Trig<double> {
   static constexpr double kIncMax = 0.025;
   // |d| <= 0.25 for step_med: the first dropped terms d^15/15!, d^16/16! < 1e-21
   static constexpr double kIncMed = 0.25;
-  static constexpr int kResync = IKG_RESYNC64;
+  static constexpr int kResync = 128;
   IKG_HD static inline void step_med(double d, double& s, double& c) {
     const double d2 = d * d;
     const double sd =
@@ -1214,12 +1078,7 @@ IKG_HD inline void pose_error(const T* Rh, const T* th, const T* RT, const T* tT
 #pragma unroll
   for (int i = 0; i < 3; ++i) d[i] = tT[i] - th[i];
   matvec3_t(Rh, d, pm);
-  if constexpr (IKG_ABL & 2) {
-    e[0] = pm[0]; e[1] = pm[1]; e[2] = pm[2];
-    e[3] = T(0.5) * (Rm[7] - Rm[5]); e[4] = T(0.5) * (Rm[2] - Rm[6]); e[5] = T(0.5) * (Rm[3] - Rm[1]);
-  } else {
-    log6(Rm, pm, e);
-  }
+  log6(Rm, pm, e);
 }
 
 // The same error expressed in the axes of the frame (Rh, th) is given in:
@@ -1234,12 +1093,7 @@ IKG_HD inline void pose_error_aligned(const T* Rh, const T* th, const T* RT, con
   matmul3_nt(RT, Rh, Rw);
 #pragma unroll
   for (int i = 0; i < 3; ++i) d[i] = tT[i] - th[i];
-  if constexpr (IKG_ABL & 2) {
-    e[0] = d[0]; e[1] = d[1]; e[2] = d[2];
-    e[3] = T(0.5) * (Rw[7] - Rw[5]); e[4] = T(0.5) * (Rw[2] - Rw[6]); e[5] = T(0.5) * (Rw[3] - Rw[1]);
-  } else {
-    log6_iter<T, COLD, ROW3>(Rw, d, e, tk, resync);
-  }
+  log6_iter<T, COLD, ROW3>(Rw, d, e, tk, resync);
 }
 
 // ---------------------------------------------------------------- 6x6 solve, 2 RHS
@@ -1403,11 +1257,6 @@ IKG_HD inline void trig_advance(T qc, const T* qa, const T* q_old, bool resync, 
   }
 #pragma unroll
   for (int j = 0; j < 7; ++j) big |= any_of(fabs(d[j]) > T(Trig<T>::kIncMax));
-  if constexpr (IKG_ABL & 1) {  // timing ablation: no incremental trig
-#pragma unroll
-    for (int j = 0; j < 7; ++j) sn[j] += d[j];
-    return;
-  }
   if (big) {
     trig_exact(qc, qa, sn, cs);
   } else {
@@ -1646,9 +1495,7 @@ IKG_HD inline void arm_solve_wrist(const ArmState<T>& st, T* u, T* v, typename L
 template <typename T, class SP>
 IKG_HD inline void arm_solve(const ArmState<T>& st, T* u, T* v, T& alpha, T& beta,
                              typename LaneT<T>::M* near_singular = nullptr, T tau = T(0)) {
-  if constexpr (IKG_ABL & 4) {
-    for (int k = 0; k < 6; ++k) { u[k] = st.e[k] + st.org[k][0]; v[k] = st.ax[k][1]; }
-  } else if constexpr (SP::wrist) {
+  if constexpr (SP::wrist) {
     arm_solve_wrist(st, u, v, near_singular, tau);
   } else {
     static_assert(!is_packed<T>, "the generic QR solve runs in the pair layout");
@@ -1684,7 +1531,7 @@ IKG_HD inline void arm_solve(const ArmState<T>& st, T* u, T* v, T& alpha, T& bet
 // path (pinv(J) e is invariant to the frame J and e are written in, and the
 // joint-space u, v are the same): ~100 fewer fp64 operations per update.
 template <class SP>
-constexpr bool kFrame1 = IKG_FRAME1 && SP::axis(0) == 2 && SP::axis(1) == 2 && SP::axis(2) == 1 &&
+constexpr bool kFrame1 = SP::axis(0) == 2 && SP::axis(1) == 2 && SP::axis(2) == 1 &&
                          SP::axis(3) == 1 && SP::axis(4) == 0 && SP::axis(5) == 1 && SP::axis(6) == 2 &&
                          !SP::prot && SP::wrist && SP::fold_hand;
 
@@ -2321,13 +2168,10 @@ __device__ inline void pinv_step_lq(const T (&A)[6][8], int, T* dq, T& s) {
   for (int k = 0; k < 6; ++k) dq[k] = z[1 + k] + f * p[1 + k];
 }
 
-// The guard's branch as an out-of-line call (IKG_COLD_CALL): the loop is then
+// The guard's branch as an out-of-line call: the loop is then
 // register-allocated as if the branch did not exist, and only a taken branch
 // pays for saving the loop's state around the call (round 3: the inlined
 // branch cost the never-taken loop 3-4% at C2 / C3).
-#ifndef IKG_COLD_CALL
-#define IKG_COLD_CALL 1
-#endif
 template <typename T>
 struct ColdIO {  // the branch's inputs and outputs, copied only when it is taken
   ArmStateF1<T> st;
@@ -2352,8 +2196,7 @@ __device__ inline void pinv_step_f1(const KModel<typename LaneT<T>::E>* __restri
   arm_solve_f1<T, SP>(m, arm, st, sn, cs, u, v, alpha, beta);
   bool need;
   pinv_step_tail<T, X>(u, v, alpha, beta, m->sing_beta, dq, s, need);
-  if (__builtin_expect(IKG_SING_GUARD && need, 0)) {
-#if IKG_COLD_CALL
+  if (__builtin_expect(need, 0)) {
     if constexpr ((is_f64<T> || is_packed<T>) && COLD) {
       ColdIO<T> io;
       io.st = st;
@@ -2368,7 +2211,6 @@ __device__ inline void pinv_step_f1(const KModel<typename LaneT<T>::E>* __restri
       s = io.s;
       return;
     }
-#endif
     T A[6][8];
     arm_system_f1<T, SP>(m, arm, st, sn, cs, A);
     pinv_step_lq<T, X>(A, arm, dq, s);
@@ -2384,7 +2226,7 @@ __device__ inline void pinv_step_cf(const ArmState<T>& st, int arm, T tau, T bou
   // a small relative pivot (truncated by the QR, or a small 3 x 3
   // determinant) travels as an out-of-bound |v|^2
   pinv_step_tail(u, v, alpha, vsel(bad, T(3e38), beta), bound, dq, s, need);
-  if (__builtin_expect(IKG_SING_GUARD && need, 0)) {
+  if (__builtin_expect(need, 0)) {
     T A[6][8];
     arm_system(st, A);
     pinv_step_lq(A, arm, dq, s);
@@ -2392,7 +2234,7 @@ __device__ inline void pinv_step_cf(const ArmState<T>& st, int arm, T tau, T bou
 }
 
 // This lane's arm limits (pair layout), loaded once per solve when the
-// registers are available (IKG_LANE_LIMITS).
+// registers are available.
 template <typename T>
 struct ArmLimits {
   T lo[kArmDof], hi[kArmDof];

@@ -172,7 +172,7 @@ void emu_one(const ikg::KModel<T>& m, const ikg::KParams<T>& prm, bool damped, c
       const T* dq = dqa[arm];
       ArmLimits<T> lim;
       load_limits(&m, arm, lim);
-      arm_update(&m, arm, prm.dt, s, dq, qc[arm], qa[arm], IKG_LANE_LIMITS ? &lim : nullptr);
+      arm_update(&m, arm, prm.dt, s, dq, qc[arm], qa[arm], &lim);
       if (f1)
         (med ? trig_advance_f1<T, true> : trig_advance_f1<T, false>)(&m, arm, qc[arm], qa[arm], q_old[arm],
                                                                      (it % Trig<T>::kResync) == 0, sn[arm], cs[arm]);

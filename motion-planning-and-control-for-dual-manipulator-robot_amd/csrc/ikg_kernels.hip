@@ -35,30 +35,21 @@ namespace ikg {
 // One 64-lane wave per workgroup holding `ppw` problems on lanes [0, 2 ppw).
 // A wave's issue cost does not depend on how many lanes are active, so small
 // batches are spread with ppw < 32 to occupy every SIMD.
-#ifndef IKG_WPE
-#define IKG_WPE 0
-#endif
 // Waves per SIMD the register allocation must leave room for: the guarded
 // step's LQ branch (pinv_step_f1) is cold, so spilling around it keeps the
 // loop at the occupancy it had without it (fp64 226 VGPRs: 2 waves; fp32
 // 103: 4); without the bound its registers took fp64 to 1 wave per SIMD.
-// IKG_PAIR_MINW64: the fp64 bound as a build knob (a
-// 3-wave build, at most 168 VGPRs, A/B'd in the throughput regime)
-#ifndef IKG_PAIR_MINW64
-#define IKG_PAIR_MINW64 2
-#endif
+// (a 3-wave fp64 build, at most 168 VGPRs, was A/B'd in
+// the throughput regime.)
+constexpr int kPairMinWaves64 = 2;
 template <typename T, bool DAMPED, class SP>
-constexpr int kPairMinWaves = (kFrame1<SP> && !DAMPED) ? (sizeof(T) == 8 ? IKG_PAIR_MINW64 : 4) : 1;
+constexpr int kPairMinWaves = (kFrame1<SP> && !DAMPED) ? (sizeof(T) == 8 ? kPairMinWaves64 : 4) : 1;
 
 template <typename T, bool DAMPED, class SP, bool MED = false, int REC = 0>
 __global__ __launch_bounds__(64)
-#if IKG_WPE
-__attribute__((amdgpu_waves_per_eu(1, IKG_WPE)))
-#else
 // the resume kernel (REC = 2): few waves at most launches, so the registers of
 // one wave per SIMD (no spills)
 __attribute__((amdgpu_waves_per_eu(REC == 2 ? 1 : kPairMinWaves<T, DAMPED, SP>)))
-#endif
 void ikg_pair_batch_kernel(const KModel<T>* __restrict__ gm, KParams<T> prm,
                                                             const T* __restrict__ targets,
                                                             const T* __restrict__ q0, int64_t q0_stride, int64_t B,

@@ -88,8 +88,8 @@ inline void build_kmodel(const ikg_model_desc& d, KModel<T>& k) {
   // arm solve's cancellation (u - s v with |u|, |v| ~ 1/tau) would cost more
   // than ~1e-12 (fp64) / 1e-5 (fp32) of the step, so the pair takes the
   // 6 x 7 LQ form instead
-  k.sing_beta = (T)(sizeof(T) == 8 ? IKG_SING_BETA64 : IKG_SING_BETA32);
-  k.sing_tau = (T)(sizeof(T) == 8 ? IKG_SING_TAU64 : IKG_SING_TAU32);
+  k.sing_beta = (T)(sizeof(T) == 8 ? kSingBeta64 : kSingBeta32);
+  k.sing_tau = (T)(sizeof(T) == 8 ? kSingTau64 : kSingTau32);
   // test knobs, read when the tables are built: IKG_SING_BETA=0 (with
   // IKG_SING_TAU=1e30 for the generic path) sends every update through the
   // LQ form.  A value must parse whole as a finite number >= 0; anything else

@@ -192,10 +192,7 @@ hipError_t launch_packed_batch(const KModel<float>* dmodel, const KParams<float>
                        (const float*)a.q0, a.q0_stride, a.B, a.S, (float*)a.q_out, a.converged, a.iters,
                        (float*)a.err_out, ra);
   };
-#ifndef IKG_PACKED_REC
-#define IKG_PACKED_REC 1
-#endif
-  if (IKG_PACKED_REC && a.recs.rec) {  // collision continuation checkpoints (0: A/B knob, the trajectory kernel instead)
+  if (a.recs.rec) {  // collision continuation checkpoints
     // the resume launch (a.rec_list, REC = 2) takes the cap the batch launch took (need from a.B)
     if (need == 1 && capped_ok<1, 1>())
       a.rec_list ? go(ikg_packed_batch_kernel<SpecNextage, 1, true, 2>) : go(ikg_packed_batch_kernel<SpecNextage, 1, true, 1>);

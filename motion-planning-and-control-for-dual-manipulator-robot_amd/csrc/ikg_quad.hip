@@ -213,7 +213,7 @@ void ikg_quad_batch_kernel(const KModel<T>* __restrict__ m, KParams<T> prm,
     sn[4] = qb<0>(sB), cs[4] = qb<0>(cB);
     sn[5] = qb<1>(sB), cs[5] = qb<1>(cB);
     sn[6] = qb<2>(sB), cs[6] = qb<2>(cB);
-    ThetaTrack<T>* tkp = (IKG_THETA_TRACK && is_f64<T>) ? &tk : nullptr;
+    ThetaTrack<T>* tkp = is_f64<T> ? &tk : nullptr;
     ArmStateF1<T> st;
     x = quad_fk_error<T, SP>(m, arm, j, sn, cs, RT, tT, st, tkp, (it % Trig<T>::kResync) == 0);
     T dq[6], s;

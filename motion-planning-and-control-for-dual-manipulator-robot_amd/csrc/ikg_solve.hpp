@@ -45,9 +45,6 @@ IKG_HD inline int rec_len(int n_passive) { return kRecPassive + ((n_passive + 3)
 
 template <typename T>
 __device__ __forceinline__ void store_block8(T* dst, const T (&v)[8]) {
-#if defined(IKG_REC_NOSTORE)  // timing ablation only: records not written (answers wrong)
-  (void)dst, (void)v;
-#else
   struct alignas(16) V16 {
     T x[16 / sizeof(T)];
   };
@@ -59,7 +56,6 @@ __device__ __forceinline__ void store_block8(T* dst, const T (&v)[8]) {
     for (int e = 0; e < per; ++e) b.x[e] = v[k * per + e];
     reinterpret_cast<V16*>(dst)[k] = b;
   }
-#endif
 }
 
 template <typename T>
@@ -78,9 +74,6 @@ __device__ __forceinline__ void load_block8(const T* src, T (&v)[8]) {
 
 template <typename T>
 __device__ __forceinline__ void store_block4(T* dst, const T (&v)[4]) {
-#if defined(IKG_REC_NOSTORE)  // timing ablation only
-  (void)dst, (void)v;
-#else
   struct alignas(16) V16 {
     T x[16 / sizeof(T)];
   };
@@ -92,7 +85,6 @@ __device__ __forceinline__ void store_block4(T* dst, const T (&v)[4]) {
     for (int e = 0; e < per; ++e) b.x[e] = v[k * per + e];
     reinterpret_cast<V16*>(dst)[k] = b;
   }
-#endif
 }
 
 // ---- window checkpoints (round 6: the records' window form)
@@ -125,11 +117,7 @@ constexpr int kCkQ = 0, kCkSn = 8, kCkCs = 16, kCkTk = 24, kCkL = 7;
 template <typename E>
 constexpr int kWinOf = kWin;
 template <typename T>
-#ifdef IKG_REC_RS_ABL  // timing ablation only: the batch loop's own resync period (resumed windows wrong)
-constexpr int kRsRec = Trig<T>::kResync;
-#else
 constexpr int kRsRec = Trig<T>::kResync < kWin ? Trig<T>::kResync : kWin;  // divides kWin
-#endif
 template <typename E>
 IKG_HD inline int rec_windows(int max_iters) { return max_iters / kWinOf<E> + 1; }
 template <typename E>
@@ -268,23 +256,14 @@ struct PassOut {
 // update, in a branch the whole wave skips unless a lane passes for the first
 // time (once per problem), and goes on iterating; its later iterates are never
 // stored.  "Done" is one 64-bit scalar mask and the loop leaves on scalar
-// tests.  IKG_SCALAR_RETIRE=0: the per-lane break, for timing A/Bs.
-#ifndef IKG_SCALAR_RETIRE
-#define IKG_SCALAR_RETIRE 1
-#endif
+// tests.
 // The same loop lays its rare wave-uniform branches (the exact acos, the near-pi axis, the
-// exact trig) off the common path (ikg_device.hpp IKG_RARELY).  IKG_COLD_PATHS=0: in line.
-#ifndef IKG_COLD_PATHS
-#define IKG_COLD_PATHS 1
-#endif
+// exact trig) off the common path (ikg_device.hpp IKG_RARELY).
 // The same loop has a second copy for waves whose targets are all rotations about z
-// (pair_batch_body).  IKG_ZT=0: the general loop for every wave.
-#ifndef IKG_ZT
-#define IKG_ZT 1
-#endif
+// (pair_batch_body).
 // the instantiations that take it: record-free, frame-1 (lambda = 0), pair layout
 template <typename T, bool DAMPED, class SP, int REC>
-constexpr bool kScalarRetire = IKG_SCALAR_RETIRE && IKG_UNIFORM && !REC && kFrame1<SP> && !DAMPED && !is_packed<T>;
+constexpr bool kScalarRetire = !REC && kFrame1<SP> && !DAMPED && !is_packed<T>;
 
 // REC = 1: from the first passing iterate on, the window checkpoints go into
 // this problem's fixed slots (ikg_capi.hip sizes the launches so the slots fit
@@ -314,7 +293,7 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
   static_assert(!REC || F1, "records: the frame-1 loop only");
   // lanes retire through the scalar done mask (po: where their outputs go)
   constexpr bool RETIRE = kScalarRetire<T, DAMPED, SP, REC>;
-  constexpr bool COLD = RETIRE && IKG_COLD_PATHS;
+  constexpr bool COLD = RETIRE;
   static_assert(!ZT || RETIRE, "z-aligned targets: the record-free frame-1 pair loop only");
   uint64_t done = 0, live = 0;  // RETIRE: the lanes whose outputs are written / that entered the loop
   if constexpr (RETIRE) live = __builtin_amdgcn_ballot_w64(true);
@@ -351,60 +330,21 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
   }
   bool conv = false;
   T x, xo;  // squared error norms of this lane's hand and the partner's
-#if IKG_LANE_LIMITS
   ArmLimits<T> lim;
   if constexpr (!is_packed<T>) load_limits(m, arm, lim);
   const ArmLimits<T>* limp = is_packed<T> ? nullptr : &lim;
-#else
-  const ArmLimits<T>* limp = nullptr;
-#endif
-#ifdef IKG_PAD_OPS
-  // timing experiment: IKG_PAD_OPS independent fp64 FMAs per iteration (ILP 8)
-  T pad[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) pad[i] = qc + T(i);
-#endif
-#ifdef IKG_PAD_SALU
-  // timing experiment: IKG_PAD_SALU scalar ALU instructions per iteration (add, xor), one chain
-  // in one register: the kernel is at its scalar register limit
-  uint32_t spad = __builtin_amdgcn_readfirstlane(prm.max_iters);
-#endif
 #ifdef IKG_STAGE_CLOCK
   unsigned long long sc_acc[5] = {0, 0, 0, 0, 0}, sc_t0 = 0, sc_t1 = 0, sc_r0, sc_r1, sc_l0, sc_l1;
   IKG_RSTAMP(sc_r0);
   IKG_STAMP(sc_l0);
 #endif
   for (;;) {
-#ifdef IKG_PAD_OPS
-#pragma unroll
-    for (int k = 0; k < IKG_PAD_OPS / 8; ++k)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) pad[i] = pad[i] * T(0.999999) + T(1e-7);
-#endif
-#ifdef IKG_PAD_SALU
-#pragma unroll
-    for (int k = 0; k < IKG_PAD_SALU; ++k) spad = (k & 1) ? spad ^ (uint32_t)it : spad + 0x9e3779b9u;
-#endif
-#ifdef IKG_PAD_BRN  // IKG_PAD_BRN wave-uniform branches per iteration, never taken (exec is not 0)
-#pragma unroll
-    for (int k = 0; k < IKG_PAD_BRN; ++k) asm volatile("s_cbranch_execz .Likg_brn%=\n.Likg_brn%=:" ::);
-#endif
-#ifdef IKG_PAD_BRT  // IKG_PAD_BRT wave-uniform branches per iteration, always taken, each over 64 bytes of code
-#pragma unroll
-    for (int k = 0; k < IKG_PAD_BRT; ++k)
-      asm volatile(
-          "s_cbranch_execnz .Likg_brt%=\n"
-          ".rept 16\n\ts_nop 0\n.endr\n"
-          ".Likg_brt%=:" ::);
-#endif
-#if IKG_UNIFORM
     // every live lane of the wave has run the same number of updates, so the
     // count (and the resync / max_iters tests on it) is wave-uniform: scalar
     // (the pair layout's resume kernel too: a wave's tasks share their window)
     if constexpr (!is_packed<T>) it = __builtin_amdgcn_readfirstlane(it);
-#endif
     // fp32: atan2f is as cheap as the tracked angle (measured)
-    ThetaTrack<T>* tkp = (IKG_THETA_TRACK && is_f64<T>) ? &tk : nullptr;
+    ThetaTrack<T>* tkp = is_f64<T> ? &tk : nullptr;
     // the record-writing kernels resync at every window start (kRsRec)
     constexpr int kRs = REC ? kRsRec<T> : Trig<T>::kResync;
     const bool resync = RETIRE ? rs_phase == 0 : (it % kRs) == 0;
@@ -557,14 +497,12 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
     sc_acc[2] += sc_t1 - sc_t0;
 #endif
     arm_update(m, arm, T(prm.dt), s, dq, qc, qa, limp);
-#ifndef IKG_REC_NOL_ABL  // timing ablation only: no path length (window boxes wrong)
     if constexpr (REC == 1) {  // the window's path length: this update's largest joint step
       T mv = fabs(qc - q_old[0]);
 #pragma unroll
       for (int k = 0; k < kArmDof; ++k) mv = fmax(mv, fabs(qa[k] - q_old[k + 1]));
       L = L + mv;
     }
-#endif
     ++it;
 #ifdef IKG_STAGE_CLOCK
     IKG_STAMP(sc_t0);
@@ -596,15 +534,6 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
 #pragma unroll
     for (int k = 0; k < 5; ++k) atomicAdd(&g_stage[4 + k], sc_acc[k]);
   }
-#endif
-#ifdef IKG_PAD_OPS
-  T ps = T(0);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) ps += pad[i];
-  if (any_of(ps == T(-12345.678))) it = -1;  // never true; keeps the padding live
-#endif
-#ifdef IKG_PAD_SALU
-  if (spad == 0x7ffffff1u) it = -1;  // keeps the padding live
 #endif
   if constexpr (REC) {
     if constexpr (REC == 2) {  // records only: the scan writes the outputs
@@ -743,7 +672,6 @@ __device__ inline void pair_batch_body(const KModel<T>* __restrict__ m, const KP
   } else if constexpr (kScalarRetire<T, DAMPED, SP, REC>) {  // a pair that passes writes its outputs in the loop
     const PassOut<T> po{qrow, q_out + p * m->nq, conv_out ? conv_out + p : nullptr,
                         iters_out ? iters_out + p : nullptr, err_out ? err_out + p * 2 : nullptr};
-#if IKG_ZT
     // every lane still here holds a z-aligned target: the wave runs the ZT loop (one choice per
     // launch; the lanes that left above are in neither ballot).  Both loops give an aligned
     // problem the same bits, so its answer does not depend on which targets share its wave.
@@ -759,9 +687,6 @@ __device__ inline void pair_batch_body(const KModel<T>* __restrict__ m, const KP
       asm volatile("; general loop" : "+v"(qc));
       if (solve_pair<T, DAMPED, SP, MED>(m, prm, arm, RT, tT, qc, qa, it, conv, nrm, other, nullptr, &po)) return;
     }
-#else
-    if (solve_pair<T, DAMPED, SP, MED>(m, prm, arm, RT, tT, qc, qa, it, conv, nrm, other, nullptr, &po)) return;
-#endif
   } else {
     solve_pair<T, DAMPED, SP, MED>(m, prm, arm, RT, tT, qc, qa, it, conv, nrm, other);
   }

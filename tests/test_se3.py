@@ -239,7 +239,7 @@ def test_identity_rotation_is_exact(results, fx, name):
 
 
 def test_pair_and_packed_fp32_loops_agree_bitwise(results, fx):
-    """E5 and E6 on the same float inputs (IKG_FAST_ATAN2 on for both): identical bits"""
+    """E5 and E6 on the same float inputs (both take the angle from atan2_upper): identical bits"""
     assert np.array_equal(results["E5"][1].view(np.int64), results["E6"][1].view(np.int64))
 
 

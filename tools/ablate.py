@@ -1,5 +1,6 @@
-"""Interleaved timing of ablation builds (tools/build_ablations.sh) in ONE
-process: B targets, fixed 1000 iterations (eps=1e-37), kernel time by HIP events."""
+"""Interleaved timing of several library builds (tools/build_variants.sh, tools/ab.sh)
+in ONE process: B targets, fixed 1000 iterations (eps=1e-37), kernel time by HIP events.
+usage: ablate.py B f64|f32 "glob of libraries [glob ...]"."""
 import ctypes as C
 import glob
 import os
@@ -15,9 +16,11 @@ from ikgrasp import _lib  # noqa: E402
 from ikgrasp.model import load_nextage  # noqa: E402
 from ikgrasp.workload import uniform_targets  # noqa: E402
 
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
-dtype = sys.argv[2] if len(sys.argv) > 2 else "f64"
-pattern = sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "motion-planning-and-control-for-dual-manipulator-robot_amd/ikgrasp/_native/abl/*.so")
+if len(sys.argv) < 4:
+    sys.exit(__doc__)
+B = int(sys.argv[1])
+dtype = sys.argv[2]
+pattern = sys.argv[3]
 libs = [f for pat in pattern.split() for f in sorted(glob.glob(pat))]
 dev = torch.device("cuda", 0)
 tdt = torch.float64 if dtype == "f64" else torch.float32
