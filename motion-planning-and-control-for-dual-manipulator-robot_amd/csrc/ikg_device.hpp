@@ -176,10 +176,24 @@ IKG_HD inline bool wave_any(bool b) {
 #endif
   return b;
 }
+// a or b in any lane: one ballot per compare (the ballot of a disjunction goes through a select
+// and a second compare)
+template <typename T>
+IKG_HD inline bool wave_any2(bool a, bool b) {
+#ifdef __HIP_DEVICE_COMPILE__
+  if constexpr (!LaneT<T>::packed) return (__builtin_amdgcn_ballot_w64(a) | __builtin_amdgcn_ballot_w64(b)) != 0;
+#endif
+  return a || b;
+}
 // COLD (the record-free frame-1 pair loop): the branch is laid out off the
 // common path, which then falls through it; a taken branch costs a lone wave ~20 cycles.
 // A macro: the hint is read where it is the branch's own condition, not through a call.
 #define IKG_RARELY(COLD, c) ((COLD) ? __builtin_expect((c), false) : (c))
+// log6_iter<COLD>'s rare branch held taken (fp64): false in every product unit.  The host
+// emulator (ikg_host_emu.hip) defines the macro before this header to read its own switch.
+#ifndef IKG_EMU_SMALL_ANGLE
+#define IKG_EMU_SMALL_ANGLE() false
+#endif
 IKG_HD inline bool mnot(bool m) { return !m; }
 IKG_HD inline v2i mnot(v2i m) { return m == 0; }
 IKG_HD inline bool mor(bool a, bool b) { return a || b; }
@@ -688,6 +702,50 @@ IKG_HD inline T fma1(T a, T b, T c) {
     return __builtin_fmaf(a, b, c);
 }
 
+// log6_iter's fp64 forms by band of the angle, each lane selecting its own: the small-angle series
+// below kPrec3, the near-pi axis (behind a wave-uniform branch), the mid-band forms between.
+// The taken side of log6_iter<double, COLD>'s rare branch.  INVARIANT: this is the fp64 text of
+// log6_iter's in-place forms (below, "every other instantiation"), operation for operation; a
+// change to the series, the guard or the near-pi axis is made in both, and
+// tests/test_log6_rare_path.py and tests/test_gpu_rare_path.py compare the two bit for bit.
+template <typename T, bool COLD, bool ROW3>
+IKG_HD inline void log6_bands(const T* R, T theta, T t2, T st, T ct, T sx, T sy, T sz, T* w, T& alpha, T& beta) {
+  static_assert(is_f64<T> && !is_packed<T>, "the fp64 pair loop only");
+  using M = typename LaneT<T>::M;
+  const T pi = T(Prec<T>::kPi);
+  const T tiny = T(1e-300);
+  const M above = theta > T(Prec<T>::kPrec3);
+  const M below = theta < T(Prec<T>::kPrec3);
+  // one reciprocal serves theta/sin(theta) and 1/theta^2: q = 1/(theta^2 sin)
+  const T q = frcp<T>(fmax(t2 * st, tiny));
+  const T inv_t2 = st * q;
+  const T f = vsel<T>(above, theta * t2 * q, T(1));  // Pinocchio: theta/sin(theta) -> 1 below precision<3>()
+  const T hf = f * T(0.5);
+  w[0] = hf * sx;
+  w[1] = hf * sy;
+  w[2] = hf * sz;
+  // alpha = theta sin/(2(1-cos)) = theta (1+cos)/(2 sin): the second form has no
+  // cancellation below the near-pi band (there |1+cos| >= 5e-5: < 2e-14 abs.)
+  alpha = hf * (T(1) + ct);
+  const M near_pi = theta >= pi - T(1e-2);
+  if (IKG_RARELY(COLD, wave_any<T>(any_of(near_pi)))) {  // near pi (rare): the axis from the diagonal
+    const T bd = fdiv<T>(t2, T(1) - ct);
+    const T t0 = (R[0] - ct) * bd, t1 = (R[4] - ct) * bd, tt = (ROW3 ? sub_plain(R[8], ct) : R[8] - ct) * bd;
+    const T wp0 = vsel<T>(R[7] > R[5], T(1), T(-1)) * vsel<T>(t0 > T(0), sqrt(t0), T(0));
+    const T wp1 = vsel<T>(R[2] > R[6], T(1), T(-1)) * vsel<T>(t1 > T(0), sqrt(t1), T(0));
+    const T wp2 = vsel<T>(R[3] > R[1], T(1), T(-1)) * vsel<T>(tt > T(0), sqrt(tt), T(0));
+    w[0] = vsel<T>(near_pi, wp0, w[0]);
+    w[1] = vsel<T>(near_pi, wp1, w[1]);
+    w[2] = vsel<T>(near_pi, wp2, w[2]);
+    alpha = vsel<T>(near_pi, fdiv<T>(theta * st, T(2) * (T(1) - ct)), alpha);
+  }
+  // Pinocchio's series terms t2/12, t2^2/720 as products with the rounded reciprocals
+  const T as = T(1) - t2 * T(1.0 / 12) - (t2 * t2) * T(1.0 / 720);
+  const T bs = T(1.0 / 12) + t2 * T(1.0 / 720);
+  beta = vsel<T>(below, bs, (T(1) - alpha) * inv_t2);
+  alpha = vsel<T>(below, as, alpha);
+}
+
 // ROW3 (pose_error_f1's z-aligned form): R's third row is the hand rotation's third column
 // itself, not a sum of products.  Where that column's entry is a bare product the compiler
 // would contract it into the sums below that read it (one rounding less than the general form,
@@ -735,6 +793,50 @@ IKG_HD inline void log6_iter(const T* R, const T* p, T* e, ThetaTrack<T>* tk = n
     theta = atan2_upper(st, ct);  // fp32: accurate near 0 where acos is not
   }
   const T t2 = theta * theta;
+  if constexpr (is_f64<T> && COLD) {
+    T w[3], alpha, beta;
+    // the record-free frame-1 pair loop: the small-angle forms join the near-pi
+    // axis behind one wave-uniform rare branch.  A wave none of whose lanes is in either band
+    // (theta <= kPrec3, equality and NaN included, or theta >= pi - 1e-2) runs the mid-band forms
+    // alone: what log6_bands' selects pick for each such lane, so the bits are the same and no
+    // lane's value depends on its wave-mates.  There the reciprocal's guard is the identity too:
+    // R is a product of joint rotations (orthonormal to ~1e-15) and theta follows acos(ct) to
+    // ~1e-15, so st >= sin(kPrec3) - 1e-13 and t2 st > 1.8e-12.
+    // The mid-band forms come first and the branch selects over them per lane (a triangle whose
+    // taken side reads them: a two-sided branch, or one that only overwrites, leaves them a block
+    // of their own that the scheduler cannot overlap with the Jacobian work).
+    const T q = frcp<T>(t2 * st);
+    const T hf = theta * t2 * q * T(0.5);
+    w[0] = hf * sx;
+    w[1] = hf * sy;
+    w[2] = hf * sz;
+    alpha = hf * (T(1) + ct);
+    beta = (T(1) - alpha) * (st * q);
+    const bool near_pi = theta >= pi - T(1e-2);
+    const bool small = !(theta > T(Prec<T>::kPrec3)) || IKG_EMU_SMALL_ANGLE();
+    if (IKG_RARELY(COLD, wave_any2<T>(near_pi, small))) {
+      T wb[3], ab, bb;
+      log6_bands<T, COLD, ROW3>(R, theta, t2, st, ct, sx, sy, sz, wb, ab, bb);
+      const bool banded = near_pi || small;
+      w[0] = vsel<T>(banded, wb[0], w[0]);
+      w[1] = vsel<T>(banded, wb[1], w[1]);
+      w[2] = vsel<T>(banded, wb[2], w[2]);
+      alpha = vsel<T>(banded, ab, alpha);
+      beta = vsel<T>(banded, bb, beta);
+    }
+    const T wp = w[0] * p[0] + w[1] * p[1] + w[2] * p[2];
+    const T bwp = beta * wp;
+    e[0] = alpha * p[0] - T(0.5) * (w[1] * p[2] - w[2] * p[1]) + bwp * w[0];
+    e[1] = alpha * p[1] - T(0.5) * (w[2] * p[0] - w[0] * p[2]) + bwp * w[1];
+    e[2] = alpha * p[2] - T(0.5) * (w[0] * p[1] - w[1] * p[0]) + bwp * w[2];
+    e[3] = w[0];
+    e[4] = w[1];
+    e[5] = w[2];
+    return;
+  }
+  // every other instantiation: the same forms in place.  INVARIANT: log6_bands above is the copy
+  // of this text's fp64 side (routing these instantiations through it changed the packed fp32
+  // kernels' assembly); change both together.
   const T tiny = is_f64<T> ? T(1e-300) : T(1e-30f);
   const M above = theta > T(Prec<T>::kPrec3);
   const M below = theta < T(Prec<T>::kPrec3);

@@ -11,6 +11,10 @@
 #include <cstring>
 #include <vector>
 
+// ikg_emu_force_small_angle's switch, read by log6_iter<double, COLD> through this macro (the
+// product units compile it as false, ikg_device.hpp)
+thread_local bool ikg_emu_small_angle = false;
+#define IKG_EMU_SMALL_ANGLE() (::ikg_emu_small_angle)
 #include "ikg_collision.hpp"
 #include "ikg_device.hpp"
 #include "ikg_dynamics.hpp"
@@ -89,7 +93,13 @@ void emu_one(const ikg::KModel<T>& m, const ikg::KParams<T>& prm, bool damped, c
     for (int arm = 0; arm < 2; ++arm) {
       if constexpr (kFrame1<SP>) {
         if (f1) {
-          nrm[arm] = (zt ? arm_fk_error_f1<T, SP, false, true> : arm_fk_error_f1<T, SP, false, false>)(
+          // fp64: the pose error as the record-free pair loop instantiates it (COLD: log6_iter's
+          // rare branch, which ikg_emu_force_small_angle holds taken).  The checkpoint, resume and
+          // quad kernels instantiate COLD = false: the same values (a resync forces the exact angle
+          // either way, and a lane outside both bands keeps the forms the selects pick for it), but
+          // log6_iter's non-COLD fp64 text is reached only through ikg_emu_se3 (fn 4, 5) now.
+          constexpr bool CD = is_f64<T>;
+          nrm[arm] = (zt ? arm_fk_error_f1<T, SP, CD, true> : arm_fk_error_f1<T, SP, CD, false>)(
               &m, arm, sn[arm], cs[arm], RT[arm], tT[arm], s1[arm], tkp[arm], resync);
           continue;
         }
@@ -270,6 +280,11 @@ extern "C" int ikg_emu_solve(const ikg_model_desc* d, int dtype, const void* tar
 
 // The general pose-error loop for every target (on != 0), or the kernel's choice (0).
 extern "C" void ikg_emu_force_general(int on) { force_general = on != 0; }
+
+// log6_iter's rare branch (fp64 pair loop: the small-angle forms and the near-pi axis behind
+// their selects) on every update (on != 0), as a lane runs it whose wave-mates hold the branch
+// taken, or only where this problem's own angle asks for it (0); tests/test_log6_rare_path.py
+extern "C" void ikg_emu_force_small_angle(int on) { ikg_emu_small_angle = on != 0; }
 
 // The kernel's z-aligned test (z_aligned on hook_target's rotation) of n targets
 // [n][12]: out[2 i + arm] = 1 where arm's hook target of target i passes.
