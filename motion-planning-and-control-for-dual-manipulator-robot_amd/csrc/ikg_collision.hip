@@ -817,8 +817,8 @@ __device__ __forceinline__ void stretch_update(const KModel<T>* __restrict__ m, 
 // iterate in the main loop.  Out of line so that the loop gets a register
 // allocation of its own: inlined into the continuation kernel, whose live
 // state spills it to AGPRs, the same iteration issued 4.5x the VALU
-// instructions of ikg_cert_stretch_kernel's (PMC).  The caller's state is
-// saved once per stretch instead.
+// instructions of a stand-alone stretch kernel's (PMC; that kernel is retired,
+// DESIGN.md §5h).  The caller's state is saved once per stretch instead.
 template <typename T, bool DAMPED, class SP>
 __device__ __noinline__ void cert_stretch(const KModel<T>* __restrict__ m, int max_iters, T eps2, T dt, T lambda,
                                           int arm, int li, const T* RT_, const T* tT_, const T* Rr_,
@@ -881,8 +881,6 @@ __device__ __noinline__ void cert_stretch(const KModel<T>* __restrict__ m, int m
 // the register bound of the kernels before it (spills go to that branch)
 template <typename T, bool DAMPED, class SP>
 constexpr int kContMinWaves = (sizeof(T) == 4 && kFrame1<SP> && !DAMPED) ? 2 : 1;
-template <typename T, bool DAMPED, class SP>
-constexpr int kStretchMinWaves = (kFrame1<SP> && !DAMPED) ? (sizeof(T) == 8 ? 2 : 4) : 1;
 
 template <typename T, bool DAMPED, class SP, int G>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kContMinWaves<T, DAMPED, SP>)))
@@ -894,10 +892,7 @@ void ikg_collide_continue_kernel(const KModel<T>* __restrict__ m,
                                                                   uint8_t* __restrict__ conv,
                                                                   int32_t* __restrict__ iters,
                                                                   T* __restrict__ err,
-                                                                  int32_t* __restrict__ witness, int handoff,
-                                                                  int32_t* __restrict__ stretch_list,
-                                                                  int32_t* __restrict__ stretch_count,
-                                                                  T* __restrict__ stretch_rec,
+                                                                  int32_t* __restrict__ witness,
                                                                   const int32_t* __restrict__ cont_list,
                                                                   const int32_t* __restrict__ cont_count) {
   extern __shared__ __align__(16) char lds[];
@@ -945,7 +940,6 @@ void ikg_collide_continue_kernel(const KModel<T>* __restrict__ m,
       V.W->epa_wait = 0;
       V.W->gen = 0;
       V.W->budget = 0.0;
-      V.flag[3] = T(0);
     }
   }
   __syncthreads();
@@ -972,7 +966,7 @@ void ikg_collide_continue_kernel(const KModel<T>* __restrict__ m,
   // budget / Rmot of their chain joints) and the motion bound accumulated
   // against it, in registers: no LDS traffic per iteration but one int read
   int cgen = 0;
-  bool cert_live = false, handed = false;
+  bool cert_live = false;
   T Rr[7] = {};
   T qcert[7] = {}, cbudget = T(0);
   for (;;) {
@@ -981,15 +975,13 @@ void ikg_collide_continue_kernel(const KModel<T>* __restrict__ m,
 #endif
     // Certified stretch: while the witness pair provably intersects, the
     // reference's stop test cannot pass, so the IK lanes iterate alone (no
-    // LDS flags, no barriers, no joint frames).  handoff != 0: the problem
-    // leaves for ikg_cert_stretch_kernel (pair layout, the batch kernel's
-    // registers and pace) with its remaining margin; otherwise the stretch
-    // runs here.  Either way it ends at the first iterate whose errors pass
-    // once the margin is spent (redone below with a real check) or at max_iters.
+    // LDS flags, no barriers, no joint frames).  The stretch ends at the first
+    // iterate whose errors pass once the margin is spent (redone below with a
+    // real check) or at max_iters.
     // the group's decision (its IK lanes'), for every lane of the group
     const bool go_ik = active && li < 2 && cert_live && passive_clamped;
     const bool go = __shfl(go_ik ? 1 : 0, lane0) != 0;
-    if (!handoff && go) {
+    if (go) {
       // every lane of the group runs the stretch, the others mirroring their
       // arm's IK lane bit for bit: a wave issues the same instruction stream
       // either way, but with 2 live lanes out of 64 it ran 2.5x slower
@@ -1015,24 +1007,6 @@ void ikg_collide_continue_kernel(const KModel<T>* __restrict__ m,
       if (li < 2) {
         if (arm == 0) V.q[m->root_q] = qc;
         for (int k = 0; k < kArmDof; ++k) V.q[arm ? m->arm_q[1][k] : m->arm_q[0][k]] = qa[k];
-      }
-    }
-    if (handoff && go_ik) {
-      if (li == 0) {
-        V.flag[3] = T(1);
-        stretch_rec[p * kStretchRec] = cbudget;
-      }
-#pragma unroll
-      for (int k = 0; k < 7; ++k) {
-        stretch_rec[p * kStretchRec + 1 + 7 * arm + k] = Rr[k];
-        stretch_rec[p * kStretchRec + 15 + 7 * arm + k] = qcert[k];
-      }
-    }
-    if (handoff) {
-      __syncthreads();
-      if (active && V.flag[3] != T(0)) {
-        handed = true;
-        active = false;
       }
     }
     __syncthreads();
@@ -1132,105 +1106,11 @@ void ikg_collide_continue_kernel(const KModel<T>* __restrict__ m,
 #endif
   if (started) {
     for (int j = li; j < nq; j += LG) q_out[p * nq + j] = V.q[j];
-    if (handed) {  // continues in ikg_cert_stretch_kernel: pending (-2 - pair), listed
-      if (li == 0) {
-        iters[p] = it;
-        witness[p] = -2 - V.W->pair;
-        stretch_list[atomicAdd(stretch_count, 1)] = (int32_t)p;
-      }
-    } else {
-      if (li < 2) err[p * 2 + arm] = sqrt(nrm);
-      if (li == 0) {
-        conv[p] = success ? 1 : 0;
-        iters[p] = it;
-        witness[p] = -1;  // final
-      }
-    }
-  }
-}
-
-// Certified stretches handed off by the continuation (stretch_list): pair
-// layout as in ikg_pair_batch_kernel (two lanes per problem, up to 32 per
-// wave, spread over the chip when few), the batch kernel's chest-frame
-// iteration, with the continuation's margin test: while the motion bound
-// stays below the remaining certified margin the witness pair still
-// intersects, so the stop test of inverse_geometry.py:70 cannot pass.  Ends
-// at max_iters (final: not converged) or at the first iterate whose errors
-// pass once the margin is spent (witness[p] back to the pair: the next
-// continuation launch redoes that iterate with a real check).
-template <typename T, bool DAMPED, class SP>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 ? kStretchMinWaves<T, DAMPED, SP> : 1)))
-void ikg_cert_stretch_kernel(const KModel<T>* __restrict__ m, KParams<T> prm,
-                                                              const T* __restrict__ targets, int64_t S_per_target,
-                                                              T* __restrict__ q_out, uint8_t* __restrict__ conv,
-                                                              int32_t* __restrict__ iters, T* __restrict__ err,
-                                                              int32_t* __restrict__ witness,
-                                                              const int32_t* __restrict__ stretch_list,
-                                                              const int32_t* __restrict__ stretch_count,
-                                                              const T* __restrict__ stretch_rec, int ppw_min) {
-  const int n = *stretch_count;
-  const int lane = threadIdx.x, arm = lane & 1;
-  const int nb = (int)gridDim.x;
-  // ppw_min < 0 (timing experiment): one problem per wave, every lane pair
-  // of the wave computing it, lanes 0/1 storing
-  const bool mirror = ppw_min < 0;
-  const int ppw = mirror ? 1 : min(32, max(ppw_min, (n + nb - 1) / nb));
-  const bool writer = !mirror || lane < 2;
-  const int nq = m->nq;
-  for (int base = (int)blockIdx.x * ppw; base < n; base += nb * ppw) {
-    const int i = base + (mirror ? 0 : lane >> 1);
-    if ((!mirror && lane >= 2 * ppw) || i >= n) continue;  // both lanes of a pair together
-    const int64_t p = stretch_list[i];
-    const int64_t tgt = S_per_target > 1 ? p / S_per_target : p;
-    T RT[9], tT[3], qc, qa[kArmDof], sn[7], cs[7], Rr[7], qcert[7];
-    hook_target(m, arm, targets + tgt * 12, RT, tT);
-    T* qrow = q_out + p * nq;
-    qc = qrow[m->root_q];
-#pragma unroll
-    for (int k = 0; k < kArmDof; ++k) qa[k] = qrow[arm ? m->arm_q[1][k] : m->arm_q[0][k]];
-    if constexpr (kStretchF1<SP, DAMPED>)
-      trig_exact_f1(m, arm, qc, qa, sn, cs);
-    else
-      trig_exact(qc, qa, sn, cs);
-    ArmLimits<T> lim;
-    load_limits(m, arm, lim);
-    const T budget = stretch_rec[p * kStretchRec];
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-      Rr[k] = stretch_rec[p * kStretchRec + 1 + 7 * arm + k];
-      qcert[k] = stretch_rec[p * kStretchRec + 15 + 7 * arm + k];
-    }
-    int it = iters[p];
-    T x;
-    bool final = false;
-    ThetaTrack<T> tk{};
-    for (int r = 0;; ++r) {
-      T dq[6], s;
-      x = stretch_step<T, DAMPED, SP>(m, prm, arm, sn, cs, RT, tT, dq, s, &tk,
-                                      r == 0 || (it % Trig<T>::kResync) == 0);
-      const T xo = pair_swap(x);
-      const T em = motion_bound(qc, qa, qcert, Rr);
-      const T et = em + pair_swap(em);
-      if (it >= prm.max_iters) {  // loop exhausted (:100): the last errors are reported
-        final = true;
-        break;
-      }
-      if (x < prm.eps2 && xo < prm.eps2) {
-        if (!(et < budget)) break;
-        if (arm == 0) SKIP_STAT(1, 1);
-      }
-      stretch_update<T, DAMPED, SP>(m, prm, arm, s, dq, it, qc, qa, sn, cs, lim);
-      ++it;
-    }
-    if (!writer) continue;
-    if (arm == 0) qrow[m->root_q] = qc;
-#pragma unroll
-    for (int k = 0; k < kArmDof; ++k) qrow[arm ? m->arm_q[1][k] : m->arm_q[0][k]] = qa[k];
-    if (final) err[p * 2 + arm] = sqrt(x);
-    if (arm == 0) {
+    if (li < 2) err[p * 2 + arm] = sqrt(nrm);
+    if (li == 0) {
+      conv[p] = success ? 1 : 0;
       iters[p] = it;
-      if (final) conv[p] = 0;
-      witness[p] = final ? -1 : -2 - witness[p];
+      witness[p] = -1;  // final
     }
   }
 }
@@ -1382,17 +1262,16 @@ struct TrajWs {
   int64_t slots;      // slots per parity
   int by_p = 0;       // records, counts and it0 indexed by problem (the pair kernel's records)
   int cert = 1;       // inscribed-ball certificates before the witness tests (IKG_SCAN_CERT=0: off)
-  // round -2 (window checkpoints, ikg_solve.hpp kWinOf): problem i = index i of
-  // the batch, every converged one checked first, then a colliding one's
-  // windows tested against certificates; wit_out[i] = the colliding pair
-  // found when some window is left to regenerate (flagged in wmask), -1 if
-  // none, not converged or answered
+  // round -2 (window checkpoints, ikg_solve.hpp kWinOf): a problem of the
+  // pre-screen's colliding list has its windows tested against certificates;
+  // wit_out[p] = its colliding pair when some window is left to regenerate
+  // (flagged in wmask), -1 if answered
   int32_t* wit_out = nullptr;
   const T* ck = nullptr;        // the batch kernel's window checkpoints
   uint32_t* wmask = nullptr;    // per problem, the windows left (mask_words each): written by round -2, read by round 0
-  // round -2 over the whole batch: a problem with windows left is appended to
-  // this list (its order is the atomic's: no answer depends on it -- a
-  // problem's records, resume tasks and scan are its own), else compacted after
+  // round -2: a problem with windows left is appended to this list (its order
+  // is the atomic's: no answer depends on it -- a problem's records, resume
+  // tasks and scan are its own)
   int32_t* app_list = nullptr;
   int32_t* app_count = nullptr;
   const uint64_t* rmask = nullptr;  // round 0: per problem and window, the iterates the resume kernel recorded
@@ -1405,7 +1284,7 @@ struct TrajWs {
   // waves in all, at most kScanSplitMax per problem); each wave's first
   // collision-free passing record goes to best[p] (atomicMin), and the last of
   // the G waves to arrive (arrive[p]) writes the answer.  best / arrive are set
-  // by round -2 (fused) or by the host (split first check).  split_waves 0: off
+  // by round -2.  split_waves 0: off
   int32_t* best = nullptr;
   int32_t* arrive = nullptr;
   int split_waves = 0;
@@ -1420,27 +1299,16 @@ static int scan_cert() { return (int)env_int("IKG_SCAN_CERT", 1); }
 // problem up to 65,536.  The listed count is known only on the device, so the
 // grid is sized by B and waves past it return at once.  A grid of 1,024 (one
 // wave per SIMD, ~8.5 windows each at C3) took C3 + collision 2.21 ms against
-// 1.98 (profiles/r05/collision/scan_waves/); IKG_SCAN_WAVES sets it for A/Bs
+// 1.98 (profiles/r05/collision/scan_waves/)
+constexpr int64_t kScanWaves = 65536;
+static int64_t scan_waves(int64_t B) { return std::min(kScanWaves, B); }
 // IKG_BOX_COVER=0: round -2 proves no window by its box, so every problem that
 // collides at its first passing iterate has all its records regenerated and
 // scanned -- the round-5 records' work, for the tests that pin the window
 // form's answers to it (and for A/Bs)
-// The first check of a records solve: the lean pre-screen kernel checks every
-// converged problem and lists the colliding ones itself, then
-// ikg_first_check_kernel runs the window boxes over that list.  The fused form
-// (IKG_PRESCAN=1: one wave per problem of the batch for both) carries the
-// certificate code's registers into every problem's check --
-// 1 wave per SIMD in fp64, 1.6 ms for C4's 131,072-problem share; with the
-// kernels' own appends (no compaction launches) the split form is also the
-// faster at C2 (70 against 75 us) and C3 (254 against 267 us),
-// profiles/r06/records/prescan/
-static bool first_fused() { return env_flag("IKG_PRESCAN", false); }
 static int box_cover() { return env_flag("IKG_BOX_COVER", true); }
 // IKG_SCAN_SPLIT: the split scan's wave target (0: one wave per listed problem)
 static int scan_split() { return std::max(0, (int)env_int("IKG_SCAN_SPLIT", 2048)); }
-static int64_t scan_waves(int64_t B) {
-  return std::min<int64_t>(std::max(1, (int)env_int("IKG_SCAN_WAVES", 65536)), B);
-}
 // the record layout (kRec*, rec_len, store_block8) is in ikg_solve.hpp
 
 template <typename T>
@@ -1626,9 +1494,6 @@ __device__ inline bool witness_hit_lane(const KModel<T>* __restrict__ m, const K
 // the whole wave runs the full check (collide_wave's sweep): collision-free
 // is the answer, else the pair found becomes the witness and the chunk's
 // unproved records after it are tested against it.
-// round = -1 (no pre-screen): the first check of every listed problem, at the
-// iterate the batch kernel stopped at (q_out): collision-free problems are
-// final there, the others get their first witness.
 // ball_cert over the wave: lane 0 walks the chains, the lanes place a joint
 // each, lane 0 composes, then every lane runs the point search from its own
 // start (deep_point_from) and the deepest point (lowest start on a tie, as
@@ -1814,8 +1679,9 @@ __device__ inline void window_covers(const KModel<T>* __restrict__ m, const KCol
   __syncthreads();
 }
 
-// FIRST: round -2 only (ikg_first_check_kernel: the first check and the window
-// boxes, none of the records scan's code, so its registers stay the check's)
+// FIRST: round -2 only (ikg_first_check_kernel: the window boxes of the
+// pre-screen's colliding problems, none of the records scan's code, so its
+// registers stay the boxes')
 template <typename T, bool FIRST = false>
 __device__ __forceinline__ void traj_scan_body(const KModel<T>* __restrict__ m, const KCollision<T>* __restrict__ c,
                                                const T* __restrict__ targets, int64_t S_per_target,
@@ -1850,52 +1716,27 @@ __device__ __forceinline__ void traj_scan_body(const KModel<T>* __restrict__ m, 
                     : 1;
   for (int64_t t = blk; t < (int64_t)n_ent * G; t += nb) {
     const int i = (int)w.rbase + (int)(t / G), g = (int)(t % G);
-    // answered by an earlier scan: window r - 1's, or (no pre-screen: witness0
-    // null) the first checks' before window 0
-    if ((round > 0 || (round == 0 && !witness0)) && w.done[i]) continue;  // wave-uniform
-    if constexpr (FIRST) round = -2;
-    // FIRST: every problem of the batch (its first check, then the window
-    // boxes), or with witness0 the pre-screen's colliding list (boxes only)
-    const bool fused = FIRST && !witness0;
-    const int64_t p = fused ? (int64_t)i : (int64_t)clist[i];
+    if (round > 0 && w.done[i]) continue;  // answered by window r - 1's scan (wave-uniform)
+    const int64_t p = clist[i];
     if (FIRST && w.best && lane == 0) {  // the split scan's per-problem state (a listed problem passes here)
       w.best[p] = kScanNone;
       w.arrive[p] = 0;
-    }
-    if (fused && !conv[p]) {  // wave-uniform
-      if (lane == 0) w.wit_out[p] = -1;
-      continue;
     }
     const int64_t t_idx = S_per_target > 1 ? p / S_per_target : p;
     if (lane < 12) tgt[lane] = targets[t_idx * 12 + lane];
     if (lane < nq) S.par[lane] = m->jparent[lane];
     if (lane == 0) {  // the pre-screen's colliding pair, else the one the last window ended with
-      const int wp0 = fused || (round < 0 && !FIRST) ? -1 : witness0 && (round == 0 || FIRST) ? witness0[p] : w.cst[i].pair;
+      const int wp0 = FIRST || round == 0 ? witness0[p] : w.cst[i].pair;
       W.pair = wp0 >= 0 && wp0 < c->n_pairs ? wp0 : -1;  // a witness is only a hint: never trust an index
       W.cert_ok = 0;
       bc_pair = -1;
       bc_fail = -1;
     }
-    if (round < 0 && lane < nq) S.q[lane] = q_out[p * nq + lane];
     __syncthreads();
-    if (round < 0) {
-      bool col = true;  // FIRST over the pre-screen's list: colliding (W.pair the pair it found)
-      if (!FIRST || fused) {
-        stage_trig_par(m, S);
-        __syncthreads();
-        col = collide_wave<T, true>(m, c, S, tgt, W);
-      }
-      if (lane == 0) {
-        if (FIRST)
-          w.wit_out[p] = -1;  // window_covers sets it when windows are left to regenerate
-        else if (col)
-          w.cst[i].pair = W.pair;
-        else
-          w.done[i] = 1;  // :70 errors pass and no collision: final as the batch kernel left it
-      }
+    if constexpr (FIRST) {  // a problem of the pre-screen's list: colliding (W.pair the pair it found)
+      if (lane == 0) w.wit_out[p] = -1;  // window_covers sets it when windows are left to regenerate
       __syncthreads();
-      if constexpr (FIRST)
-        if (col && W.pair >= 0) window_covers(m, c, S, tgt, W, SL, BC, w, p, q_out, conv, iters, err);
+      if (W.pair >= 0) window_covers(m, c, S, tgt, W, SL, BC, w, p, q_out, conv, iters, err);
       continue;  // wave-uniform
     }
     const int64_t ix = w.by_p ? p : par + i;
@@ -2122,34 +1963,26 @@ __device__ __noinline__ void traj_scan(const KModel<T>* __restrict__ m, const KC
   traj_scan_body<T>(m, c, targets, S_per_target, clist, n, witness0, w, Wn, round, q_out, conv, iters, err, blk, nb);
 }
 
-// Separate launches (IKG_TRAJ_FUSE=0): window r's updates, then its scan.
-template <typename T, bool DAMPED, class SP>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kStretchMinWaves<T, DAMPED, SP>)))
-void ikg_traj_update_kernel(const KModel<T>* __restrict__ m, KParams<T> prm,
-                                                             const T* __restrict__ targets, int64_t S_per_target,
-                                                             const T* __restrict__ q_out,
-                                                             const int32_t* __restrict__ iters,
-                                                             const int32_t* __restrict__ clist,
-                                                             const int32_t* __restrict__ count, TrajWs<T> w, int Wn,
-                                                             int r) {
-  traj_window<T, DAMPED, SP>(m, prm, targets, S_per_target, q_out, iters, clist, *count, w, Wn, r, (int)blockIdx.x,
-                             (int)gridDim.x);
-}
-
-// Round -2 over the batch (one wave per problem, grid-stride): the first
-// check at the batch kernel's iterate and the window boxes (window_covers);
-// with witness0, over the pre-screen's colliding list (clist, *count): the
-// window boxes only
+// Round -2 (one wave per problem, grid-stride) over the pre-screen's colliding
+// list (clist, *count; witness0 its pairs): the window boxes (window_covers).
+// The first check of a records solve is the two together: the lean pre-screen
+// kernel checks every converged problem and lists the colliding ones itself,
+// then this kernel runs over that list.  A fused form (one wave per problem of
+// the batch for both; retired) carried the certificate code's
+// registers into every problem's check -- 1 wave per SIMD in fp64, 1.6 ms for
+// C4's 131,072-problem share; with the kernels' own appends (no compaction
+// launches) the split form is also the faster at C2 (70 against 75 us) and C3
+// (254 against 267 us), profiles/r06/records/prescan/
 constexpr int kFcWaves64 = 1;  // waves per SIMD the fp64 first check and records scan are compiled for
 template <typename T>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 ? 3 : kFcWaves64)))
 void ikg_first_check_kernel(const KModel<T>* __restrict__ m, const KCollision<T>* __restrict__ c,
-                            const T* __restrict__ targets, int64_t S_per_target, int64_t B,
+                            const T* __restrict__ targets, int64_t S_per_target,
                             const int32_t* __restrict__ clist, const int32_t* __restrict__ count,
                             const int32_t* __restrict__ witness0, TrajWs<T> w, T* __restrict__ q_out,
                             uint8_t* __restrict__ conv, int32_t* __restrict__ iters, T* __restrict__ err) {
-  traj_scan_body<T, true>(m, c, targets, S_per_target, clist, count ? *count : (int)B, witness0, w, 0, -2, q_out, conv,
-                          iters, err, (int)blockIdx.x, (int)gridDim.x);
+  traj_scan_body<T, true>(m, c, targets, S_per_target, clist, *count, witness0, w, 0, -2, q_out, conv, iters, err,
+                          (int)blockIdx.x, (int)gridDim.x);
 }
 
 // fp32: at most 168 VGPRs, so 3 waves fit a SIMD as before the certificate
@@ -2170,8 +2003,7 @@ void ikg_traj_scan_kernel(const KModel<T>* __restrict__ m,
 
 // Launch r of rounds + 1: window r's updates on the first `tblocks`
 // workgroups, window r - 1's scan on the others (both read only what launch
-// r - 1 wrote; the two windows use different record buffers).  first != 0
-// (no pre-screen): launch 0's scan part runs the first checks (round -1).
+// r - 1 wrote; the two windows use different record buffers).
 template <typename T, bool DAMPED, class SP>
 __global__ __launch_bounds__(64) void ikg_traj_kernel(const KModel<T>* __restrict__ m,
                                                       const KCollision<T>* __restrict__ c, KParams<T> prm,
@@ -2179,7 +2011,7 @@ __global__ __launch_bounds__(64) void ikg_traj_kernel(const KModel<T>* __restric
                                                       const int32_t* __restrict__ clist,
                                                       const int32_t* __restrict__ count,
                                                       const int32_t* __restrict__ witness0, TrajWs<T> w, int Wn,
-                                                      int r, int rounds, int tblocks, int first, T* __restrict__ q_out,
+                                                      int r, int rounds, int tblocks, T* __restrict__ q_out,
                                                       uint8_t* __restrict__ conv, int32_t* __restrict__ iters,
                                                       T* __restrict__ err) {
   const int n = *count;
@@ -2187,7 +2019,7 @@ __global__ __launch_bounds__(64) void ikg_traj_kernel(const KModel<T>* __restric
   if (blk < tblocks) {
     if (r < rounds)
       traj_window<T, DAMPED, SP>(m, prm, targets, S_per_target, q_out, iters, clist, n, w, Wn, r, blk, tblocks);
-  } else if (r > 0 || first) {
+  } else if (r > 0) {
     traj_scan<T>(m, c, targets, S_per_target, clist, n, witness0, w, Wn, r - 1, q_out, conv, iters, err,
                  blk - tblocks, (int)gridDim.x - tblocks);
   }
@@ -2203,70 +2035,28 @@ hipError_t launch_collision(const KModel<T>* dm, const KCollision<T>* dc, const 
   return hipGetLastError();
 }
 
-// problems per continuation wave (IKG_CONT_G=1 selects one per wave; timing knob)
-static int cont_groups() {
-  static const int v = env_int("IKG_CONT_G", 4) == 1 ? 1 : 4;
-  return v;
-}
-
 // stream-ordered workspace of one continuation: witness / state per problem
-// (>= 0: continue with this pair, -1: final, <= -2: stretch pending), the
-// stretch list and its count, the stretch records (remaining margin + Rmot)
-template <typename T>
+// (>= 0: continue with this pair, -1: final), the pre-screen's list and the
+// continuation's, and their counts
 struct ContWs {
   int32_t* wit;
-  int32_t* list;    // stretch hand-off list
-  int32_t* count;   // its length; [1]: length of clist
-  int32_t* clist;   // the continuation's problems (ikg_compact_*_kernel)
-  T* rec;
+  int32_t* list;    // records solve: the pre-screen's colliding problems; else the compaction's chunk counts
+  int32_t* count;   // [1]: length of clist, [2]: length of list
+  int32_t* clist;   // the continuation's problems (ikg_compact_*_kernel, or the first check's appends)
 };
 
-// Continuation launches that hand certified stretches to the stretch kernel
-// before the last one, which runs any remaining stretch itself.  Every round
-// is a grid-wide sync, and a problem whose margin runs out mid-stretch waits
-// for the round's longest stretch before its re-check.  With the
-// continuation's problems compacted (4 per wave), the in-kernel stretch wins
-// at every measured size, so the default is 0 rounds.  Measured
-// (tools/probe/rounds.sh, kernel ms per solve, 0/1/2 rounds): C2 fp64
-// B=4096: 2.39/3.35/3.19; C3 fp32 B=65536: 5.10/5.38/5.71.  Before the
-// compaction (problems in place, ~0.5 per wave): C2 2.47/3.45/3.17, C3
-// 6.06/5.20/5.72.  IKG_HANDOFF_ROUNDS overrides (the tests run both paths).
-static int handoff_rounds() { return std::min(64, std::max(0, (int)env_int("IKG_HANDOFF_ROUNDS", 0))); }
-
-// least problems per stretch wave (IKG_STRETCH_PPW; timing knob)
-static int stretch_ppw() {
-  static const int v = std::min(32, std::max(-1, (int)env_int("IKG_STRETCH_PPW", 32)));
-  return v == 0 ? 1 : v;
-}
-
-template <typename T, bool DAMPED, class SP, int G>
-static void launch_continue_g(const KModel<T>* dm, const KCollision<T>* dc, const KParams<T>& prm,
-                              const BatchArgs& a, int nq, int ng, const ContWs<T>& w, hipStream_t s) {
-  const size_t lds = (size_t)G * group_lds_bytes<T>(nq, ng);
-  const dim3 grid((unsigned)((a.B + G - 1) / G));
-  // stretch kernel: enough waves to give every SIMD of the chip one, at most
-  const unsigned sgrid = (unsigned)std::min<int64_t>(1024, a.B);
-  const int rounds = handoff_rounds();
-  for (int r = 0; r <= rounds; ++r) {
-    const int handoff = r < rounds;
-    if (handoff) (void)hipMemsetAsync(w.count, 0, sizeof(int32_t), s);
-    hipLaunchKernelGGL((ikg_collide_continue_kernel<T, DAMPED, SP, G>), grid, dim3(64), lds, s, dm, dc, prm,
-                       (const T*)a.targets, a.S, a.B, (T*)a.q_out, a.converged, a.iters, (T*)a.err_out, w.wit,
-                       handoff, w.list, w.count, w.rec, (const int32_t*)w.clist, (const int32_t*)(w.count + 1));
-    if (handoff)
-      hipLaunchKernelGGL((ikg_cert_stretch_kernel<T, DAMPED, SP>), dim3(sgrid), dim3(64), 0, s, dm, prm,
-                         (const T*)a.targets, a.S, (T*)a.q_out, a.converged, a.iters, (T*)a.err_out, w.wit,
-                         (const int32_t*)w.list, (const int32_t*)w.count, (const T*)w.rec, stretch_ppw());
-  }
-}
-
+// The interleaved continuation: kContG problems per wave.  A certified stretch
+// runs inside the kernel (cert_stretch): handing it to a kernel of its own
+// between continuation launches lost at every measured size.
+constexpr int kContG = 4;
 template <typename T, bool DAMPED, class SP>
 static void launch_continue_t(const KModel<T>* dm, const KCollision<T>* dc, const KParams<T>& prm,
-                              const BatchArgs& a, int nq, int ng, const ContWs<T>& w, hipStream_t s) {
-  if (cont_groups() == 1)
-    launch_continue_g<T, DAMPED, SP, 1>(dm, dc, prm, a, nq, ng, w, s);
-  else
-    launch_continue_g<T, DAMPED, SP, 4>(dm, dc, prm, a, nq, ng, w, s);
+                              const BatchArgs& a, int nq, int ng, const ContWs& w, hipStream_t s) {
+  const size_t lds = (size_t)kContG * group_lds_bytes<T>(nq, ng);
+  const dim3 grid((unsigned)((a.B + kContG - 1) / kContG));
+  hipLaunchKernelGGL((ikg_collide_continue_kernel<T, DAMPED, SP, kContG>), grid, dim3(64), lds, s, dm, dc, prm,
+                     (const T*)a.targets, a.S, a.B, (T*)a.q_out, a.converged, a.iters, (T*)a.err_out, w.wit,
+                     (const int32_t*)w.clist, (const int32_t*)(w.count + 1));
 }
 
 // IKG_CONT_TRAJ=0 selects the interleaved continuation (the tests run both).
@@ -2274,10 +2064,6 @@ static void launch_continue_t(const KModel<T>* dm, const KCollision<T>* dc, cons
 // iterates (kTrajBudget), so the interleaved one runs there.
 constexpr int64_t kTrajMaxB = 262144;
 static bool cont_traj(int64_t B) { return env_flag("IKG_CONT_TRAJ", B <= kTrajMaxB); }
-
-// IKG_TRAJ_FUSE=0: the updates and the scan of a window as separate launches
-// (no overlap of window r + 1's updates with window r's scan)
-static bool traj_fuse() { return env_flag("IKG_TRAJ_FUSE", true); }
 
 // record window per problem: kTrajWindow iterates per (update, scan) round,
 // fewer (at least 16) when two buffers of Wn records for every problem of the
@@ -2296,7 +2082,7 @@ __global__ __launch_bounds__(256) void ikg_fill_i32_kernel(int32_t* __restrict__
 
 template <typename T, bool DAMPED, class SP>
 static hipError_t launch_traj_t(const KModel<T>* dm, const KCollision<T>* dc, const KParams<T>& prm,
-                                const BatchArgs& a, int nq, const ContWs<T>& cw, bool first, hipStream_t s) {
+                                const BatchArgs& a, int nq, const ContWs& cw, hipStream_t s) {
   // every joint is the root, an arm joint or passive (ikg_model_build.hpp)
   const size_t RL = (size_t)rec_len(std::max(0, nq - 1 - 2 * kArmDof)), B = (size_t)a.B;
   const size_t full = (size_t)prm.max_iters + 1;
@@ -2320,55 +2106,30 @@ static hipError_t launch_traj_t(const KModel<T>* dm, const KCollision<T>* dc, co
   w.slots = (int64_t)B;
   w.cert = scan_cert();
   hipLaunchKernelGGL(ikg_fill_i32_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, w.done, a.B, 0);
-  const int32_t* wit0 = first ? nullptr : (const int32_t*)cw.wit;
+  const int32_t* wit0 = (const int32_t*)cw.wit;
   const int32_t* clist = (const int32_t*)cw.clist;
   const int32_t* cnt = (const int32_t*)(cw.count + 1);
   // updates: full waves of 32 problems, at most one wave per SIMD; scan: one
   // wave per problem, grid-stride
   const int tblocks = (int)std::min<int64_t>(1024, (a.B + 31) / 32);
   const int sblocks = (int)std::min<int64_t>(1024, a.B);
-  if (!traj_fuse()) {
-    for (int r = first ? -1 : 0; r < rounds; ++r) {
-      if (r >= 0)
-        hipLaunchKernelGGL((ikg_traj_update_kernel<T, DAMPED, SP>), dim3(tblocks), dim3(64), 0, s, dm, prm,
-                           (const T*)a.targets, a.S, (const T*)a.q_out, (const int32_t*)a.iters, clist, cnt, w, Wn, r);
-      hipLaunchKernelGGL((ikg_traj_scan_kernel<T>), dim3(sblocks), dim3(64), 0, s, dm, dc, (const T*)a.targets,
-                         a.S, clist, cnt, wit0, w, Wn, r, (T*)a.q_out, a.converged, a.iters, (T*)a.err_out);
-    }
-  }
-  for (int r = 0; traj_fuse() && r <= rounds; ++r) {
-    const int nblk = tblocks + (r > 0 || first ? sblocks : 0);
+  for (int r = 0; r <= rounds; ++r) {
+    const int nblk = tblocks + (r > 0 ? sblocks : 0);
     hipLaunchKernelGGL((ikg_traj_kernel<T, DAMPED, SP>), dim3(nblk), dim3(64), 0, s, dm, dc, prm,
-                       (const T*)a.targets, a.S, clist, cnt, wit0, w, Wn, r, rounds, tblocks, first ? 1 : 0,
-                       (T*)a.q_out, a.converged, a.iters, (T*)a.err_out);
+                       (const T*)a.targets, a.S, clist, cnt, wit0, w, Wn, r, rounds, tblocks, (T*)a.q_out, a.converged,
+                       a.iters, (T*)a.err_out);
   }
   return ws.finish(hipGetLastError());
 }
 
-
-// listed for the trajectory continuation without a pre-screen: every problem
-// whose errors passed in the batch kernel (marker >= 0 for the compaction)
-__global__ __launch_bounds__(256) void ikg_mark_converged_kernel(const uint8_t* __restrict__ conv, int64_t B,
-                                                                 int32_t* __restrict__ mark) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < B) mark[i] = conv[i] ? 0 : -1;
-}
-
-// Pre-screen before the trajectory continuation (default), or
-// IKG_TRAJ_PRESCREEN=0: every converged problem runs the updates and the first
-// checks run beside window 0's updates, in its first launch.  That form took
-// C2 with the collision term from 1.64 to 1.57 ms, but one in three runs of
-// tests/test_gpu_graph.py gave a replay that differed from the direct solve
-// (cause not found), so it stays an opt-in experiment.
-static bool traj_prescreen() { return env_flag("IKG_TRAJ_PRESCREEN", true); }
-
+// The trajectory windows, or the interleaved continuation where they do not
+// run (cont_traj) or their record buffers do not fit
 template <typename T, bool DAMPED, class SP>
 static hipError_t launch_continue_sel(const KModel<T>* dm, const KCollision<T>* dc, const KParams<T>& prm,
-                                      const BatchArgs& a, int nq, int ng, const ContWs<T>& w, hipStream_t s,
-                                      bool first) {
+                                      const BatchArgs& a, int nq, int ng, const ContWs& w, hipStream_t s) {
   if (cont_traj(a.B)) {
-    const hipError_t err = launch_traj_t<T, DAMPED, SP>(dm, dc, prm, a, nq, w, first, s);
-    if (err != hipErrorOutOfMemory || first) return err;
+    const hipError_t err = launch_traj_t<T, DAMPED, SP>(dm, dc, prm, a, nq, w, s);
+    if (err != hipErrorOutOfMemory) return err;
     (void)hipGetLastError();  // no room for the record buffers: the interleaved continuation needs none
   }
   launch_continue_t<T, DAMPED, SP>(dm, dc, prm, a, nq, ng, w, s);
@@ -2376,14 +2137,15 @@ static hipError_t launch_continue_sel(const KModel<T>* dm, const KCollision<T>* 
 }
 
 // The records solve: the batch kernel wrote window checkpoints from each
-// problem's first passing iterate (ikg_solve.hpp kWinOf): (1) one wave per
-// problem of the batch checks it there and, when it collides, tests every
-// window's box against a certificate at that iterate (round -2); (2) the
-// problems with a window left are listed; (3) the batch kernel regenerates
-// their records from that window on (resume launch); (4) the records scan
+// problem's first passing iterate (ikg_solve.hpp kWinOf): (1) the pre-screen
+// checks every converged problem there and, for a colliding one, the first
+// check tests every window's box against a certificate at that iterate
+// (round -2); (2) the problems with a window left are listed; (3) the batch
+// kernel regenerates their records from that window on (resume launch);
+// (4) the records scan
 template <typename T>
 static hipError_t records_solve(const KModel<T>* dm, const KCollision<T>* dc, const KParams<T>& prm,
-                                const BatchArgs& a, int spec, const ContWs<T>& w, hipStream_t s) {
+                                const BatchArgs& a, int spec, const ContWs& w, hipStream_t s) {
   const int split = scan_split();
   const ScanLayout l(a.B, mask_words<T>(prm.max_iters), sizeof(TrajCert<T>), rec_windows<T>(prm.max_iters), split > 0);
   Workspace ws(a.ws_owner, s, "scan");
@@ -2417,18 +2179,12 @@ static hipError_t records_solve(const KModel<T>* dm, const KCollision<T>* dc, co
   tf.app_list = w.clist;
   tf.app_count = w.count + 1;
   (void)hipMemsetAsync(w.count + 1, 0, 2 * sizeof(int32_t), s);
-  if (first_fused()) {  // one wave per problem of the batch: the first check and the window boxes
-    hipLaunchKernelGGL((ikg_first_check_kernel<T>), dim3((unsigned)std::min<int64_t>(a.B, int64_t(1) << 20)), dim3(64),
-                       0, s, dm, dc, (const T*)a.targets, a.S, a.B, (const int32_t*)nullptr,
-                       (const int32_t*)nullptr, (const int32_t*)nullptr, tf, (T*)a.q_out, a.converged, a.iters,
-                       (T*)a.err_out);
-  } else {  // the pre-screen lists the colliding (w.list, count w.count[2]), the window boxes run over that list
-    hipLaunchKernelGGL((ikg_prescreen_kernel<T>), dim3((unsigned)a.B), dim3(64), 0, s, dm, dc, (const T*)a.q_out,
-                       (const T*)a.targets, a.S, a.B, (const uint8_t*)a.converged, w.wit, w.list, w.count + 2);
-    hipLaunchKernelGGL((ikg_first_check_kernel<T>), dim3((unsigned)scan_waves(a.B)), dim3(64), 0, s, dm, dc,
-                       (const T*)a.targets, a.S, a.B, (const int32_t*)w.list, (const int32_t*)(w.count + 2),
-                       (const int32_t*)w.wit, tf, (T*)a.q_out, a.converged, a.iters, (T*)a.err_out);
-  }
+  // the pre-screen lists the colliding (w.list, count w.count[2]), the window boxes run over that list
+  hipLaunchKernelGGL((ikg_prescreen_kernel<T>), dim3((unsigned)a.B), dim3(64), 0, s, dm, dc, (const T*)a.q_out,
+                     (const T*)a.targets, a.S, a.B, (const uint8_t*)a.converged, w.wit, w.list, w.count + 2);
+  hipLaunchKernelGGL((ikg_first_check_kernel<T>), dim3((unsigned)scan_waves(a.B)), dim3(64), 0, s, dm, dc,
+                     (const T*)a.targets, a.S, (const int32_t*)w.list, (const int32_t*)(w.count + 2),
+                     (const int32_t*)w.wit, tf, (T*)a.q_out, a.converged, a.iters, (T*)a.err_out);
   // the listed problems' records hold rec_slots problems (ikg_capi.hip
   // records capacity): the resume kernel and the scan run in rounds of that
   // many list entries -- launched for every round the batch could need, a
@@ -2457,28 +2213,21 @@ static hipError_t records_solve(const KModel<T>* dm, const KCollision<T>* dc, co
 }
 
 // Pre-screen, compaction and continuation (the trajectory windows, or the
-// interleaved continuation).  Without a pre-screen the trajectory
-// continuation's first launch runs the first checks, so every converged
-// problem is listed.
+// interleaved continuation).
 template <typename T>
 static hipError_t prescreen_continue(const KModel<T>* dm, const KCollision<T>* dc, const KParams<T>& prm,
-                                     const BatchArgs& a, int spec, int nq, int ng, const ContWs<T>& w,
+                                     const BatchArgs& a, int spec, int nq, int ng, const ContWs& w,
                                      hipStream_t s) {
-  const bool first = cont_traj(a.B) && !traj_prescreen();
-  if (first)
-    hipLaunchKernelGGL(ikg_mark_converged_kernel, dim3((unsigned)((a.B + 255) / 256)), dim3(256), 0, s,
-                       (const uint8_t*)a.converged, a.B, w.wit);
-  else
-    hipLaunchKernelGGL((ikg_prescreen_kernel<T>), dim3((unsigned)a.B), dim3(64), 0, s, dm, dc, (const T*)a.q_out,
-                       (const T*)a.targets, a.S, a.B, (const uint8_t*)a.converged, w.wit);
-  // listed: witness >= 0 (the chunk counts borrow the stretch list, written only after)
+  hipLaunchKernelGGL((ikg_prescreen_kernel<T>), dim3((unsigned)a.B), dim3(64), 0, s, dm, dc, (const T*)a.q_out,
+                     (const T*)a.targets, a.S, a.B, (const uint8_t*)a.converged, w.wit);
+  // listed: witness >= 0 (the chunk counts go to w.list, which this route uses for nothing else)
   const unsigned nb = (unsigned)((a.B + kCompactChunk - 1) / kCompactChunk);
   hipLaunchKernelGGL(ikg_compact_count_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)w.wit, a.B, w.list);
   hipLaunchKernelGGL(ikg_compact_write_kernel, dim3(nb), dim3(256), 0, s, (const int32_t*)w.wit, a.B,
                      (const int32_t*)w.list, w.clist, w.count + 1);
   hipError_t ec = hipSuccess;
   by_spec(spec, prm.lambda > T(0), [&](auto D, auto sp) {
-    ec = launch_continue_sel<T, decltype(D)::value, decltype(sp)>(dm, dc, prm, a, nq, ng, w, s, first);
+    ec = launch_continue_sel<T, decltype(D)::value, decltype(sp)>(dm, dc, prm, a, nq, ng, w, s);
   });
   return ec;
 }
@@ -2489,12 +2238,11 @@ hipError_t launch_collide_continue(const KModel<T>* dm, const KCollision<T>* dc,
   if (a.B <= 0) return hipSuccess;
   if (a.B > 0x7fffffff) return hipErrorInvalidValue;
   // stream-ordered workspace: the pre-screen's witness pair per problem
-  const ContLayout l(a.B, sizeof(T) * kStretchRec);
+  const ContLayout l(a.B);
   Workspace ws(a.ws_owner, s, "cont");
   const hipError_t e = ws.alloc(l);
   if (e != hipSuccess) return e;
-  const ContWs<T> w{ws.at<int32_t>(l.wit), ws.at<int32_t>(l.list), ws.at<int32_t>(l.count), ws.at<int32_t>(l.clist),
-                    ws.at<T>(l.rec)};
+  const ContWs w{ws.at<int32_t>(l.wit), ws.at<int32_t>(l.list), ws.at<int32_t>(l.count), ws.at<int32_t>(l.clist)};
   const hipError_t ec = a.recs.rec_used && *a.recs.rec_used ? records_solve<T>(dm, dc, prm, a, spec, w, s)
                                                             : prescreen_continue<T>(dm, dc, prm, a, spec, nq, ng, w, s);
   return ws.finish(ec != hipSuccess ? ec : hipGetLastError());

@@ -57,10 +57,6 @@ struct CollideScratch {
 // Expanding-polytope scratch (epa_depth_lb): at most kEpaIters expansions of
 // the starting tetrahedron.
 constexpr int kEpaIters = 5;
-// continuation -> stretch kernel record per problem: the certified margin,
-// Rmot of the root + left arm joints and of (0 +) the right arm's, then the
-// certified iterate's values of the same joints per arm
-constexpr int kStretchRec = 32;
 constexpr int kEpaV = 4 + kEpaIters;
 constexpr int kEpaF = 2 * kEpaV - 4;
 struct EpaScratch {

@@ -34,14 +34,13 @@ struct WsLayout {
   void pad(size_t bytes) { total += bytes; }  // allocated after the last array, never filled
 };
 
-// "cont", one continuation: witness / state per problem, the stretch hand-off
-// list, the continuation's problems, a 256-byte block of counts, and the
-// stretch records (`stretch_bytes` per problem, the allocation's unrounded tail)
+// "cont", one continuation: witness / state per problem, the pre-screen's
+// colliding list (or the compaction's chunk counts), the continuation's
+// problems, and a 256-byte block of counts
 struct ContLayout : WsLayout {
-  int wit, list, clist, count, rec;
-  ContLayout(size_t B, size_t stretch_bytes)
-      : wit(add(4 * B, kInt)), list(add(4 * B, kInt)), clist(add(4 * B, kInt)), count(add(256, kInt)),
-        rec(add(stretch_bytes * B, kFloat, 1)) {}
+  int wit, list, clist, count;
+  explicit ContLayout(size_t B)
+      : wit(add(4 * B, kInt)), list(add(4 * B, kInt)), clist(add(4 * B, kInt)), count(add(256, kInt)) {}
 };
 
 // "traj", the trajectory windows: two parities of Wn records of `rec_bytes`

@@ -69,15 +69,14 @@ def test_collision_batch_large_is_consistent(csolver, col_cases):
 
 # continuation schedule: the default (trajectory first: ikg_traj_kernel's
 # recorded iterates scanned by ikg_traj_scan_kernel), and the interleaved
-# continuation (IKG_CONT_TRAJ=0) with its certified stretches inside the
-# continuation kernel (0 rounds) or handed to ikg_cert_stretch_kernel (2)
-ROUNDS = [None, "0", "2"]
+# continuation (IKG_CONT_TRAJ=0, "0"), whose certified stretches run inside the
+# continuation kernel
+ROUNDS = [None, "0"]
 
 
 def _schedule(monkeypatch, rounds):
     if rounds is not None:
         monkeypatch.setenv("IKG_CONT_TRAJ", "0")
-        monkeypatch.setenv("IKG_HANDOFF_ROUNDS", rounds)
 
 
 @pytest.mark.parametrize("rounds", ROUNDS)
@@ -367,8 +366,7 @@ def test_poisoned_workspaces_give_the_same_answers(csolver, solve_cases, monkeyp
     monkeypatch.setenv("IKG_POISON", "1")
     base = csolver.solve(c["targets"], c["q0"], check_collision=True)
     assert np.array_equal(base.converged, c["success"]) and np.array_equal(base.iters, c["iters"])
-    for env in ({"IKG_TRAJ_REC": "1"}, {"IKG_TRAJ_PRESCREEN": "0"}, {"IKG_TRAJ_WINDOW": "16"},
-                {"IKG_CONT_TRAJ": "0"}):
+    for env in ({"IKG_TRAJ_REC": "1"}, {"IKG_TRAJ_WINDOW": "16"}, {"IKG_CONT_TRAJ": "0"}):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         sol = csolver.solve(c["targets"], c["q0"], check_collision=True)
@@ -403,14 +401,11 @@ def test_record_chunks_give_the_one_launch_answer(csolver, dtype, monkeypatch):
     (IKG_CK_BUDGET_MB: fp64 ~230 problems per launch); records rounds of a
     4 MB records budget (IKG_REC_BUDGET_MB: fp64 26 listed problems per
     round) -- each solved twice, all bit for bit equal.  The same with every
-    colliding problem's records regenerated (IKG_BOX_COVER=0) and with the
-    fused first check (IKG_PRESCAN=1: one wave per problem of the batch for the
-    check and the window boxes; the default pre-screens and runs the boxes over
-    its list)."""
+    colliding problem's records regenerated (IKG_BOX_COVER=0)."""
     from ikgrasp.workload import uniform_targets
     tg = uniform_targets(4096, seed=0)
     kw = dict(dtype=dtype, check_collision=True)
-    for env in ({}, {"IKG_BOX_COVER": "0"}, {"IKG_PRESCAN": "1"}):
+    for env in ({}, {"IKG_BOX_COVER": "0"}):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         one = csolver.solve(tg, np.zeros(15), **kw)

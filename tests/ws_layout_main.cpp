@@ -10,7 +10,7 @@
 //   rec_windows = 1000 / 32 + 1               = 32 windows (fp64 and fp32)
 //   mask_words  = (32 + 31) / 32              = 1
 //   ck          = (32 + 2) * 64               = 2,176 values per problem
-//   kStretchRec = 32 values, sizeof(TrajCert) = 4 bytes
+//   sizeof(TrajCert) = 4 bytes
 // al(x) rounds x up to a multiple of 256; al(4 B) = 256, 256, 16,384 for
 // B = 1, 63, 4,096.
 #include <stdio.h>
@@ -47,13 +47,11 @@ static void expect(bool ok, const char* what) {
 int main() {
   const size_t Bs[3] = {1, 63, 4096};
   const int elems[2] = {8, 4};
-  const size_t RL = 20, WINDOWS = 32, MASK_WORDS = 1, CK = 2176, STRETCH = 32, CERT = 4, NQ = 15, FULL = 1001;
+  const size_t RL = 20, WINDOWS = 32, MASK_WORDS = 1, CK = 2176, CERT = 4, NQ = 15, FULL = 1001;
 
-  // cont: 3 al(4 B) + 256 + elem * 32 * B
-  //   B = 1:     768 + 256 + 256 | 128           = 1,280 | 1,152
-  //   B = 63:    768 + 256 + 16,128 | 8,064      = 17,152 | 9,088
-  //   B = 4,096: 49,152 + 256 + 1,048,576 | 524,288 = 1,097,984 | 573,696
-  const size_t cont[3][2] = {{1280, 1152}, {17152, 9088}, {1097984, 573696}};
+  // cont: 3 al(4 B) + 256  (wit, list, clist; count), the same in fp64 and fp32
+  //   B = 1: 768 + 256; B = 63: 768 + 256; B = 4,096: 49,152 + 256
+  const size_t cont[3] = {1024, 1024, 49408};
   // scan: 5 al(4 B) + al(8 * 32 * B)  (done, wmask, cst, best, arrive; rmask), the same in fp64 and fp32
   //   B = 1: 1,280 + 256; B = 63: 1,280 + 16,128; B = 4,096: 81,920 + 1,048,576
   const size_t scan[3] = {1536, 17408, 1130496};
@@ -79,10 +77,10 @@ int main() {
   for (int b = 0; b < 3; ++b)
     for (int e = 0; e < 2; ++e) {
       const size_t B = Bs[b], el = (size_t)elems[e], ib = (4 * B + 255) / 256 * 256;
-      const ContLayout c(B, el * STRETCH);
-      check("cont", B, elems[e], c, cont[b][e], true);
-      expect(c.off[c.wit] == 0 && c.off[c.list] == ib && c.off[c.clist] == 2 * ib && c.off[c.count] == 3 * ib &&
-                 c.off[c.rec] == 3 * ib + 256 && c.len[c.rec] == el * STRETCH * B,
+      const ContLayout c(B);
+      check("cont", B, elems[e], c, cont[b], true);
+      expect(c.n == 4 && c.off[c.wit] == 0 && c.off[c.list] == ib && c.off[c.clist] == 2 * ib &&
+                 c.off[c.count] == 3 * ib && c.len[c.count] == 256,
              "cont: array order");
       for (int split = 0; split < 2; ++split) {
         const ScanLayout s(B, MASK_WORDS, CERT, WINDOWS, split != 0);

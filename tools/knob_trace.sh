@@ -4,9 +4,9 @@
 # counter-sampled (one rocprofv3 --pmc pass per variant).  Replaces round 2-5's
 # one-off probes (tools/probe/*: hand-off rounds, stretch packing, mirrored
 # lanes, icache / clock / stretch counters, C5 layouts, packed problems per wave).
-#   TAG=rounds ARGS="--collision" VARIANTS="IKG_HANDOFF_ROUNDS=0 IKG_HANDOFF_ROUNDS=2" MODE=trace tools/knob_trace.sh
-#   TAG=icache ARGS="--collision --steps 2 --warmup 1" VARIANTS="IKG_HANDOFF_ROUNDS=1,IKG_STRETCH_PPW=1 \
-#       IKG_HANDOFF_ROUNDS=1,IKG_STRETCH_PPW=32" MODE="pmc:SQ_WAVES SQ_IFETCH SQC_ICACHE_HITS SQC_ICACHE_MISSES" tools/knob_trace.sh
+#   TAG=routes ARGS="--collision" VARIANTS="base IKG_TRAJ_REC=0 IKG_CONT_TRAJ=0" MODE=trace tools/knob_trace.sh
+#   TAG=icache ARGS="--collision --steps 2 --warmup 1" VARIANTS="IKG_SCAN_SPLIT=0,IKG_SCAN_CERT=0 \
+#       IKG_SCAN_SPLIT=2048,IKG_SCAN_CERT=1" MODE="pmc:SQ_WAVES SQ_IFETCH SQC_ICACHE_HITS SQC_ICACHE_MISSES" tools/knob_trace.sh
 #   TAG=c5v ARGS="--dtype f32 --batch 512 --multistart 256" VARIANTS="base" EXTRA="--variant 0|--variant 1|--variant 2" tools/knob_trace.sh
 # A variant is NAME=VALUE[,NAME=VALUE...] or "base"; EXTRA is a |-separated
 # list of further bench.py argument sets (each run under every variant).
