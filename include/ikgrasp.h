@@ -619,6 +619,12 @@ int ikg_bezier_fit_batch(int device, const void* q0, const void* q1, const void*
  *   n_nodes [C] int32, status [C] int32:
  *     0 reached cube_rand, 1 stopped by a placement collision, 2 stopped by a
  *     failed IK, 3 cut at max_nodes (status holds -1 while a chain advances)
+ *   A chain that fills its last row at the step that reaches cube_rand is
+ *   reached (0), not cut.  Otherwise status 3 wins over a stop that the next
+ *   step would have produced: a chain whose n_nodes reaches max_nodes is cut
+ *   there, whatever its next placement or solve would have given; max_nodes = 1
+ *   cuts every chain at row 0.  The step count comes from the translations
+ *   alone: a pure rotation (equal translations) is one step whatever its angle.
  * Per step a prepare kernel, the solve and a commit kernel are enqueued on
  * `stream`; nothing waits on the host.  A host-pointer call enqueues as many
  * steps as its longest chain needs, a device-pointer call max_nodes - 1.  The

@@ -1641,19 +1641,12 @@ int ikg_project_paths(const ikg_model* model, int device, const void* q_curr, co
   const ikg::KCollision<double>* dc = nullptr;
   if (int rc = m->col.get<double>(m->mu, device, &dc)) return rc;
   // steps to enqueue: every chain ends within max_nodes - 1 steps; a host-pointer
-  // call knows the longest chain (one spare step against a last-bit difference
-  // of the device's own count; a finished chain's extra step changes nothing)
+  // call knows the longest chain (projection_host_steps)
   int64_t n_steps = (int64_t)max_nodes - 1;
   if (flags & IKG_FLAG_HOST_POINTERS) {
-    int64_t longest = 0;
-    for (int64_t c = 0; c < C; ++c) {
-      const double *pa = (const double*)cube_curr + 12 * c + 9, *pb = (const double*)cube_rand + 12 * c + 9;
-      if (!(std::sqrt((pa[0] - pb[0]) * (pa[0] - pb[0]) + (pa[1] - pb[1]) * (pa[1] - pb[1]) +
-                      (pa[2] - pb[2]) * (pa[2] - pb[2])) / step_size < 1e9))
-        return fail(IKG_EINVAL, "chain %lld: |dt| / step_size is too large", (long long)c);
-      longest = std::max<int64_t>(longest, (int64_t)ikg::projection_steps(pa, pb, step_size * (1.0 - 1e-12)));
-    }
-    n_steps = std::min(n_steps, longest);
+    int64_t bad = 0;
+    n_steps = ikg::projection_host_steps((const double*)cube_curr, (const double*)cube_rand, C, step_size, max_nodes, &bad);
+    if (n_steps < 0) return fail(IKG_EINVAL, "chain %lld: |dt| / step_size is too large", (long long)bad);
   }
   Staging st(s, flags);
   a.q_curr = (const double*)st.in(q_curr, sizeof(double) * nq * C);

@@ -5,6 +5,7 @@
 // GPU.  Built as libikgrasp_emu.so; used by tests/test_host_emu.py.  Further
 // down: the collision, dynamics, controller and closed-loop rollout arithmetic
 // on the same terms (tests/test_collision.py, test_dynamics.py, test_rollout.py).
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -951,4 +952,66 @@ extern "C" int ikg_emu_nearest(const double* nodes, int64_t cap, const int32_t* 
     dist[p] = best[0] >= 0 ? std::sqrt(d2[0]) : 0.0;
   }
   return 0;
+}
+
+// ikg_project_paths with host pointers on the CPU: the entry's step loop
+// (projection_host_steps, the zeroed outputs, prepare / solve / commit per step)
+// with the kernels' per-chain functions (project_prepare_chain,
+// project_commit_chain) run over the chains in turn and emu<double> as the
+// collision solve between them (p->check_collision as the caller sets it).  -1
+// where the entry returns IKG_EINVAL.  steps_run (may be NULL): the steps the
+// loop ran.  tests/test_projection.py.
+extern "C" int ikg_emu_project_paths(const ikg_model_desc* d, const ikg_collision_desc* cd, const double* q_curr,
+                                     const double* cube_curr, const double* cube_rand, int64_t C, double step_size,
+                                     int32_t max_nodes, const int32_t* geoms, int32_t n_geoms, const ikg_params* p,
+                                     double* robot_path, double* cube_path, int32_t* n_nodes, int32_t* status,
+                                     int32_t* steps_run) {
+  if (!d || !cd || !p || C < 0 || !(step_size > 0) || !std::isfinite(step_size) || max_nodes < 1) return -1;
+  if (n_geoms < 1 || n_geoms > IKG_MAX_GEOMS || !geoms) return -1;
+  static thread_local ikg::KCollision<double> kc;
+  ikg::build_kcollision<double>(*cd, kc);
+  if (kc.target_geom < 0) return -1;
+  ikg::ProjectArgs a{};
+  a.geoms.n = n_geoms;
+  for (int32_t k = 0; k < n_geoms; ++k) {
+    if (geoms[k] < 0 || geoms[k] >= kc.n_geoms || geoms[k] == kc.target_geom) return -1;
+    a.geoms.g[k] = geoms[k];
+  }
+  if (steps_run) *steps_run = 0;
+  if (C == 0) return 0;
+  int64_t bad = 0;
+  const int64_t n_steps = ikg::projection_host_steps(cube_curr, cube_rand, C, step_size, max_nodes, &bad);
+  if (n_steps < 0) return -1;
+  const int nq = d->nq;
+  std::vector<double> targets(12 * C), q0(nq * C), q(nq * C), err(2 * C);
+  std::vector<int32_t> iters(C), aux(2 * C);
+  std::vector<uint8_t> conv(C);
+  a.q_curr = q_curr;
+  a.cube_curr = cube_curr;
+  a.cube_rand = cube_rand;
+  a.C = C;
+  a.nq = nq;
+  a.max_nodes = max_nodes;
+  a.step_size = step_size;
+  a.robot_path = robot_path;
+  a.cube_path = cube_path;
+  a.n_nodes = n_nodes;
+  a.status = status;
+  a.targets = targets.data();
+  a.q0 = q0.data();
+  a.q = q.data();
+  a.conv = conv.data();
+  a.steps = aux.data();
+  a.free_ = aux.data() + C;
+  std::memset(robot_path, 0, sizeof(double) * nq * max_nodes * C);
+  std::memset(cube_path, 0, sizeof(double) * 12 * max_nodes * C);
+  chest_mismatch = 0;
+  for (int64_t step = 1; step <= std::max<int64_t>(n_steps, 1); ++step) {
+    for (int64_t i = 0; i < C; ++i) ikg::project_prepare_chain(&kc, a, i, (int)step);
+    if (step > n_steps) break;  // max_nodes = 1: the chains are cut at their first row
+    emu<double>(d, targets.data(), q0.data(), nq, C, p, q.data(), conv.data(), iters.data(), err.data(), nullptr, 0, cd);
+    for (int64_t i = 0; i < C; ++i) ikg::project_commit_chain(a, i, (int)step);
+    if (steps_run) *steps_run = (int32_t)step;
+  }
+  return chest_mismatch ? -3 : 0;
 }

@@ -59,81 +59,20 @@ __global__ __launch_bounds__(64) void ikg_nearest_kernel(const double* __restric
   }
 }
 
-// Step `step` (1-based) of every chain, before the solve: one thread per chain.
+// Step `step` (1-based) of every chain, before the solve: one thread per chain
+// (project_prepare_chain, ikg_planner.hpp).
 __global__ __launch_bounds__(256) void ikg_project_prepare_kernel(const KCollision<double>* __restrict__ c,
                                                                   const ProjectArgs a, int step) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.C) return;
-  const int nq = a.nq;
-  double* rp = a.robot_path + i * a.max_nodes * nq;
-  double* cp = a.cube_path + i * a.max_nodes * 12;
-  const double* A = a.cube_curr + 12 * i;
-  const double* B = a.cube_rand + 12 * i;
-  if (step == 1) {  // row 0 and the chain's step count
-    for (int k = 0; k < nq; ++k) rp[k] = a.q_curr[i * nq + k];
-    for (int k = 0; k < 12; ++k) cp[k] = A[k];
-    a.steps[i] = projection_steps(A + 9, B + 9, a.step_size);
-    a.n_nodes[i] = 1;
-    a.status[i] = a.max_nodes > 1 ? kPathLive : kPathCut;
-  }
-  int n = a.n_nodes[i];  // 1 <= n <= max_nodes by construction; the reads below are bounded regardless
-  n = n < 1 ? 1 : (n > a.max_nodes ? a.max_nodes : n);
-  const double* last_q = rp + (int64_t)(n - 1) * nq;
-  const double* last_p = cp + (int64_t)(n - 1) * 12;
-  double* tg = a.targets + 12 * i;
-  int free_ = 0;
-  if (a.status[i] == kPathLive) {  // then step <= steps: the commit ends a chain at step == steps
-    double P[12];
-    se3_interpolate(A, B, (double)step / (double)a.steps[i], P);
-    const int tgm = c->target_geom;
-    const Shape<double> S{P, P + 9, c->dims[tgm], c->kind[tgm]};
-    int hit = 0;
-    for (int k = 0; k < a.geoms.n; ++k) {
-      const int g = a.geoms.g[k];
-      const Shape<double> E{c->R[g], c->t[g], c->dims[g], c->kind[g]};
-      hit |= pair_collides(S, E) != 0;
-    }
-    free_ = !hit;
-    if (free_)
-      for (int k = 0; k < 12; ++k) tg[k] = P[k];
-  }
-  // a chain that is stopped, finished or in collision here: its last accepted
-  // placement and q, which the solve leaves after 0 updates
-  if (!free_)
-    for (int k = 0; k < 12; ++k) tg[k] = last_p[k];
-  for (int k = 0; k < nq; ++k) a.q0[i * nq + k] = last_q[k];
-  a.free_[i] = free_;
+  project_prepare_chain(c, a, i, step);
 }
 
-// After the solve: append where the chain was live, its placement free and the
-// solve converged; otherwise stop the chain.
+// After the solve: one thread per chain (project_commit_chain).
 __global__ __launch_bounds__(256) void ikg_project_commit_kernel(const ProjectArgs a, int step) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.C) return;
-  if (a.status[i] != kPathLive) return;
-  if (!a.free_[i]) {
-    a.status[i] = kPathCollision;
-    return;
-  }
-  if (!a.conv[i]) {
-    a.status[i] = kPathIkFailed;
-    return;
-  }
-  const int n = a.n_nodes[i];
-  if (n < 1 || n >= a.max_nodes) {  // the write index is bounded before the store
-    a.status[i] = kPathCut;
-    return;
-  }
-  const int nq = a.nq;
-  double* rq = a.robot_path + (i * a.max_nodes + n) * nq;
-  double* rc = a.cube_path + (i * a.max_nodes + n) * 12;
-  for (int k = 0; k < nq; ++k) rq[k] = a.q[i * nq + k];
-  for (int k = 0; k < 12; ++k) rc[k] = a.targets[12 * i + k];
-  a.n_nodes[i] = n + 1;
-  if (step >= a.steps[i])
-    a.status[i] = kPathReached;
-  else if (n + 1 >= a.max_nodes)
-    a.status[i] = kPathCut;
+  project_commit_chain(a, i, step);
 }
 
 hipError_t launch_se3_interpolate(const double* A, const double* B, const double* alpha, int64_t C, double* out,

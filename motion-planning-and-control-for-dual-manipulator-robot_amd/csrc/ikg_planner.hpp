@@ -117,6 +117,102 @@ struct ProjectArgs {
   int32_t *steps, *free_;
 };
 
+// Step `step` (1-based) of chain i, before the solve: row 0 and the step count
+// at step 1, then the step's target (where the chain is live and its placement
+// free) or the chain's last accepted row, and the warm start.
+IKG_HD inline void project_prepare_chain(const KCollision<double>* __restrict__ c, const ProjectArgs& a, int64_t i, int step) {
+  const int nq = a.nq;
+  double* rp = a.robot_path + i * a.max_nodes * nq;
+  double* cp = a.cube_path + i * a.max_nodes * 12;
+  const double* A = a.cube_curr + 12 * i;
+  const double* B = a.cube_rand + 12 * i;
+  if (step == 1) {  // row 0 and the chain's step count
+    for (int k = 0; k < nq; ++k) rp[k] = a.q_curr[i * nq + k];
+    for (int k = 0; k < 12; ++k) cp[k] = A[k];
+    a.steps[i] = projection_steps(A + 9, B + 9, a.step_size);
+    a.n_nodes[i] = 1;
+    a.status[i] = a.max_nodes > 1 ? kPathLive : kPathCut;
+  }
+  int n = a.n_nodes[i];  // 1 <= n <= max_nodes by construction; the reads below are bounded regardless
+  n = n < 1 ? 1 : (n > a.max_nodes ? a.max_nodes : n);
+  const double* last_q = rp + (int64_t)(n - 1) * nq;
+  const double* last_p = cp + (int64_t)(n - 1) * 12;
+  double* tg = a.targets + 12 * i;
+  int free_ = 0;
+  if (a.status[i] == kPathLive) {  // then step <= steps: the commit ends a chain at step == steps
+    double P[12];
+    se3_interpolate(A, B, (double)step / (double)a.steps[i], P);
+    const int tgm = c->target_geom;
+    const Shape<double> S{P, P + 9, c->dims[tgm], c->kind[tgm]};
+    int hit = 0;
+    for (int k = 0; k < a.geoms.n; ++k) {
+      const int g = a.geoms.g[k];
+      const Shape<double> E{c->R[g], c->t[g], c->dims[g], c->kind[g]};
+      hit |= pair_collides(S, E) != 0;
+    }
+    free_ = !hit;
+    if (free_)
+      for (int k = 0; k < 12; ++k) tg[k] = P[k];
+  }
+  // a chain that is stopped, finished or in collision here: its last accepted
+  // placement and q, which the solve leaves after 0 updates
+  if (!free_)
+    for (int k = 0; k < 12; ++k) tg[k] = last_p[k];
+  for (int k = 0; k < nq; ++k) a.q0[i * nq + k] = last_q[k];
+  a.free_[i] = free_;
+}
+
+// Chain i after the solve: append where the chain was live, its placement free
+// and the solve converged; otherwise stop the chain.
+IKG_HD inline void project_commit_chain(const ProjectArgs& a, int64_t i, int step) {
+  if (a.status[i] != kPathLive) return;
+  if (!a.free_[i]) {
+    a.status[i] = kPathCollision;
+    return;
+  }
+  if (!a.conv[i]) {
+    a.status[i] = kPathIkFailed;
+    return;
+  }
+  const int n = a.n_nodes[i];
+  if (n < 1 || n >= a.max_nodes) {  // the write index is bounded before the store
+    a.status[i] = kPathCut;
+    return;
+  }
+  const int nq = a.nq;
+  double* rq = a.robot_path + (i * a.max_nodes + n) * nq;
+  double* rc = a.cube_path + (i * a.max_nodes + n) * 12;
+  for (int k = 0; k < nq; ++k) rq[k] = a.q[i * nq + k];
+  for (int k = 0; k < 12; ++k) rc[k] = a.targets[12 * i + k];
+  a.n_nodes[i] = n + 1;
+  if (step >= a.steps[i])
+    a.status[i] = kPathReached;
+  else if (n + 1 >= a.max_nodes)
+    a.status[i] = kPathCut;
+}
+
+// Steps a host-pointer ikg_project_paths enqueues: every chain ends within
+// max_nodes - 1 steps, and the host knows the longest chain (one spare step
+// against a last-bit difference of the device's own count; a finished chain's
+// extra step changes nothing).  -1 with *bad = the chain whose |dt| / step_size
+// is too large for a count.
+inline int64_t projection_host_steps(const double* cube_curr, const double* cube_rand, int64_t C, double step_size,
+                                     int32_t max_nodes, int64_t* bad) {
+  int64_t longest = 0;
+  for (int64_t c = 0; c < C; ++c) {
+    const double *pa = cube_curr + 12 * c + 9, *pb = cube_rand + 12 * c + 9;
+    if (!(sqrt((pa[0] - pb[0]) * (pa[0] - pb[0]) + (pa[1] - pb[1]) * (pa[1] - pb[1]) +
+               (pa[2] - pb[2]) * (pa[2] - pb[2])) / step_size < 1e9)) {
+      *bad = c;
+      return -1;
+    }
+    const int64_t n = (int64_t)projection_steps(pa, pb, step_size * (1.0 - 1e-12));
+    longest = n > longest ? n : longest;
+  }
+  const int64_t cap = (int64_t)max_nodes - 1;
+  return cap < longest ? cap : longest;
+}
+
 hipError_t launch_se3_interpolate(const double* A, const double* B, const double* alpha, int64_t C, double* out,
                                   hipStream_t s);
 hipError_t launch_nearest(const double* nodes, int64_t cap, const int32_t* counts, const double* queries, int nq,

@@ -184,6 +184,8 @@ def project_paths(robot, q_currs, cube_currs, cube_rands, step_size=0.025, cube=
         for k in range(len(idx)):
             if col[k]:
                 active[idx[k]] = False
+        if cube is not None and C == 1:
+            setcubeplacement(robot, cube, pl[-1])  # the reference leaves the cube at the last attempt, a colliding one too
         if not go:
             continue
         q0 = np.stack([robot_paths[idx[k]][-1] for k in go])
@@ -196,8 +198,6 @@ def project_paths(robot, q_currs, cube_currs, cube_rands, step_size=0.025, cube=
                 continue
             robot_paths[c].append(sol.q[j].astype(np.float64))
             cube_paths[c].append(pl[k])
-        if cube is not None and C == 1:
-            setcubeplacement(robot, cube, pl[-1])  # the reference leaves the cube at the last attempt
     return [(robot_paths[c], cube_paths[c]) for c in range(C)]
 
 

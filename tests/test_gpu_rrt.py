@@ -17,6 +17,11 @@
   5. computepaths: three planners on M connect, each as when run alone, every
      node collision-free, ends at qinit / qgoal;
   6. a planned path goes through ikgrasp.control.maketraj.
+
+The projection on every chain outcome (statuses 0 / 1 / 2 / 3, stops after
+accepted nodes, rotated goals, batch shapes, the device-pointer route, the
+max_nodes edges) is tests/test_gpu_projection.py on
+tests/golden/projection_cases.npz; its CPU leg is tests/test_projection.py.
 """
 import os
 

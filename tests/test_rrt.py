@@ -9,6 +9,10 @@ tests/golden/make_rrt_golden.py with tests/rrt_oracle.py):
   * the emulator's SE3.Interpolate (the kernel's device function on the host)
     against the 50-digit values;
   * the emulator's nearest rule (per-row distance, argmin combine), ties included.
+
+The projection's own bookkeeping (prepare / commit per chain, the step loop) on
+the emulator is tests/test_projection.py, on tests/golden/projection_cases.npz
+(tests/golden/make_projection_golden.py, tests/projection_cases.py).
 """
 import ctypes as C
 
