@@ -738,8 +738,9 @@ __device__ __forceinline__ T cont_step(const KModel<T>* __restrict__ m, const KP
     T A[6][8], ze[6], zc[6];
     arm_system(st, A);
     arm_solve_damped(A, prm.lambda, ze, zc, alpha, beta);
-    s = chest_step(alpha + pair_swap(alpha), beta + pair_swap(beta));
-    arm_dq_damped(A, ze, zc, s, dq);
+    T t_o;
+    damped_couple(alpha, beta, pair_swap(alpha), pair_swap(beta), s, t_o);
+    arm_dq_damped(A, ze, zc, t_o, dq);
   }
   return x;
 }

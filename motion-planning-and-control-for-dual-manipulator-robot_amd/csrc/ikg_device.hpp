@@ -781,7 +781,16 @@ IKG_HD inline void log6_iter(const T* R, const T* p, T* e, ThetaTrack<T>* tk = n
       if constexpr (COLD) exact = exact || resync;
     }
     if (IKG_RARELY(COLD, wave_any<T>(exact))) {
-      const T th_x = acos(fmin(fmax(ct, T(-1)), T(1)));  // pin.log3: tr > 3 -> 0, tr < -1 -> pi
+      // pin.log3's acos((tr - 1)/2), tr > 3 -> 0, tr < -1 -> pi, as pi/2 - asin(ct); below pi/4 the
+      // angle comes from its sine instead, asin(|skew|/2): acos(ct) carries eps / theta there, and
+      // theta / sin(theta) below, with the sine from the skew part, would pass eps / theta^2
+      // (2.7e-11 at 2e-3 rad, 7e-14 at 0.04) into alpha and so |p| times that into v -- the
+      // reference's theta sin(theta) / (2 (1 - cos(theta))) of the same angle does not.  A full
+      // step (dt = 1) lands the rotation there with |p| still 0.2.  One asin call
+      // serves both: its argument is selected.
+      const bool low = ct > T(0.7);
+      const T as = asin(low ? fmin(st, T(1)) : fmin(fmax(ct, T(-1)), T(1)));
+      const T th_x = low ? as : (T(1.5707963267948966) - as) + T(6.123233995736766e-17);
       theta = exact ? th_x : theta;
     }
     if (tk) {
@@ -1254,7 +1263,7 @@ IKG_HD inline void qr_solve6(T (&A)[6][8], T* x0, T* x1, bool* near_singular = n
   }
 }
 
-// Cholesky solve of the damped arm block (J_a J_a^T + lambda I) for 2 RHS.
+// Cholesky solve of the damped arm block (J_a J_a^T + c_a c_a^T + lambda I, arm_solve_damped) for 2 RHS.
 template <typename T>
 IKG_HD inline void chol_solve6(T (&M)[6][6], T* b0, T* b1) {
 #pragma unroll
@@ -2183,7 +2192,12 @@ IKG_HD inline void arm_system_f1(const KModel<typename LaneT<T>::E>* __restrict_
 }
 
 
-// lambda > 0: z_e, z_c = (J_a J_a^T + lambda I)^-1 [e_a, c_a]; alpha = c.z_e, beta = c.z_c.
+// lambda > 0: z_e, z_c = D_a^-1 [e_a, c_a], D_a = J_a J_a^T + c_a c_a^T + lambda I (c_a: the chest
+// column); alpha = c.z_e, beta = c.z_c.  The chest column stays in the arm's block: J_a J_a^T +
+// lambda I alone is near singular wherever the six arm joints are (condition 8.6e5 at a seed row
+// whose whole J J^T + lambda I has 3.9e3), and the rank-one correction that put the column back
+// afterwards cancelled z_e against s z_c there (1.4e-10 on q after two updates at dt = 1,
+// DESIGN.md §2i).  What is left between the arms is the off-diagonal c_L c_R^T (damped_couple).
 template <typename T>
 IKG_HD inline void arm_solve_damped(const T (&A)[6][8], T lambda, T* ze, T* zc, T& alpha, T& beta) {
   T M[6][6];
@@ -2194,7 +2208,7 @@ IKG_HD inline void arm_solve_damped(const T (&A)[6][8], T lambda, T* ze, T* zc, 
       T acc = r == c ? lambda : T(0);
 #pragma unroll
       for (int k = 0; k < 6; ++k) acc += A[r][k] * A[c][k];
-      M[r][c] = acc;
+      M[r][c] = acc + A[r][7] * A[c][7];
     }
 #pragma unroll
   for (int r = 0; r < 6; ++r) {
@@ -2211,6 +2225,18 @@ IKG_HD inline void arm_solve_damped(const T (&A)[6][8], T lambda, T* ze, T* zc, 
   }
 }
 
+// The two arms' damped blocks joined: (blockdiag(D_L, D_R) + [0, c_L c_R^T; c_R c_L^T, 0]) x = e
+// gives x_a = z_e,a - t_o z_c,a with t_a = c_a . x_a, t_L = alpha_L - beta_L t_R and t_R likewise:
+// t_a = (alpha_a - beta_a alpha_o) / (1 - beta_a beta_o); the chest step is t_L + t_R.  Every
+// product is fused by hand and the sum is symmetric, so both lanes of a pair get the same s.
+template <typename T>
+IKG_HD inline void damped_couple(T alpha, T beta, T alpha_o, T beta_o, T& s, T& t_o) {
+  const T den = fma1<T>(-beta, beta_o, T(1));
+  const T na = fma1<T>(-beta, alpha_o, alpha), no = fma1<T>(-beta_o, alpha, alpha_o);
+  s = fdiv(add_plain(na, no), den);
+  t_o = fdiv(no, den);
+}
+
 // Sherman–Morrison chest step from the pair-summed scalars.
 template <typename T>
 IKG_HD inline T chest_step(T alpha_sum, T beta_sum) {
@@ -2224,10 +2250,10 @@ IKG_HD inline void arm_dq(const T* u, const T* v, T s, T* dq) {
 }
 
 template <typename T>
-IKG_HD inline void arm_dq_damped(const T (&A)[6][8], const T* ze, const T* zc, T s, T* dq) {
+IKG_HD inline void arm_dq_damped(const T (&A)[6][8], const T* ze, const T* zc, T t_o, T* dq) {
   T y[6];
 #pragma unroll
-  for (int r = 0; r < 6; ++r) y[r] = ze[r] - s * zc[r];
+  for (int r = 0; r < 6; ++r) y[r] = ze[r] - t_o * zc[r];
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
     T acc = T(0);

@@ -152,11 +152,14 @@ void emu_one(const ikg::KModel<T>& m, const ikg::KParams<T>& prm, bool damped, c
       }
     }
     for (int arm = 0; arm < 2; ++arm) {
-      sa[arm] = chest_step(al[arm] + al[1 - arm], be[arm] + be[1 - arm]);
-      if (damped)
-        arm_dq_damped(A[arm], u[arm], v[arm], sa[arm], dqa[arm]);
-      else
+      if (damped) {
+        T t_o;
+        damped_couple(al[arm], be[arm], al[1 - arm], be[1 - arm], sa[arm], t_o);
+        arm_dq_damped(A[arm], u[arm], v[arm], t_o, dqa[arm]);
+      } else {
+        sa[arm] = chest_step(al[arm] + al[1 - arm], be[arm] + be[1 - arm]);
         arm_dq(u[arm], v[arm], sa[arm], dqa[arm]);
+      }
     }
     if (!damped && (bad[0] || bad[1])) {  // pinv_step_f1 / pinv_step_cf: the per-arm pinv form
       T z[2][7], pv[2][7];

@@ -374,8 +374,9 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
       T A[6][8], ze[6], zc[6];
       arm_system(st, A);
       arm_solve_damped(A, prm.lambda, ze, zc, alpha, beta);
-      s = chest_step(alpha + pair_swap(alpha), beta + pair_swap(beta));
-      arm_dq_damped(A, ze, zc, s, dq);
+      T t_o;
+      damped_couple(alpha, beta, pair_swap(alpha), pair_swap(beta), s, t_o);
+      arm_dq_damped(A, ze, zc, t_o, dq);
     }
     }
     xo = pair_swap(x);

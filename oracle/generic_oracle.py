@@ -181,3 +181,64 @@ def computeqgrasppose(model, hooks, q0, cube_R, cube_t, hands=("LARM_EFF", "RARM
         q = np.minimum(np.maximum(model.lower, q + vq * dt), model.upper)
     _, (eL, eR) = errors(q)
     return q, False, max_iters, (np.linalg.norm(eL), np.linalg.norm(eR))
+
+
+def computeqgrasppose_mp(model, hooks, q0, cube_R, cube_t, hands=("LARM_EFF", "RARM_EFF"), max_iters=ik.MAX_ITERS,
+                         dt=ik.DT, eps=ik.EPSILON, dps=32):
+    """The loop of `computeqgrasppose` in `dps`-digit arithmetic (mpmath) from
+    the float64 model constants and inputs, rounded to float64 at the end: what
+    the float64 loop approximates (ik_oracle.computeqgrasppose_mp for a generic
+    model; the step is J^T (J J^T)^-1 e, pinv(J) e for a J of full row rank).
+    Returns (q, converged, updates, (|eL|, |eR|))."""
+    import mpmath as mp
+    mp.mp.dps = dps
+    f = mp.mpf
+    mat = lambda A: [[f(float(A[i][j])) for j in range(3)] for i in range(3)]
+    vec = lambda v: [f(float(x)) for x in v]
+    mm = lambda A, B: [[A[i][0] * B[0][j] + A[i][1] * B[1][j] + A[i][2] * B[2][j] for j in range(3)] for i in range(3)]
+    mv = lambda A, v: [A[i][0] * v[0] + A[i][1] * v[1] + A[i][2] * v[2] for i in range(3)]
+    mtv = lambda A, v: [A[0][i] * v[0] + A[1][i] * v[1] + A[2][i] * v[2] for i in range(3)]
+    tr = lambda A: [[A[j][i] for j in range(3)] for i in range(3)]
+    se3 = lambda A, B: (mm(A[0], B[0]), [A[1][i] + mv(A[0], B[1])[i] for i in range(3)])
+    cross = lambda a, b: [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+    def rod(e, q):  # exp(q [e]x)
+        s, c = mp.sin(q), 1 - mp.cos(q)
+        K = [[0, -e[2], e[1]], [e[2], 0, -e[0]], [-e[1], e[0], 0]]
+        KK = mm(K, K)
+        return [[(1 if i == j else 0) + s * K[i][j] + c * KK[i][j] for j in range(3)] for i in range(3)]
+
+    n = model.nq
+    P = [(mat(R0), vec(t0)) for R0, t0 in model.placement]
+    axes = [vec(a) for a in model.axis]
+    frames = [(model.frames[h][0], (mat(model.frames[h][1][0]), vec(model.frames[h][1][1]))) for h in hands]
+    cube = (mat(cube_R), vec(cube_t))
+    tgts = [se3(cube, (mat(hk[0]), vec(hk[1]))) for hk in hooks]
+    lo, hi = vec(model.lower), vec(model.upper)
+    q = vec(q0)
+    for it in range(max_iters + 1):
+        oMi = []
+        for j in range(n):
+            l = (mm(P[j][0], rod(axes[j], q[j])), P[j][1])
+            oMi.append(l if model.parent[j] < 0 else se3(oMi[model.parent[j]], l))
+        es, rows = [], []
+        for (j, M), (TR, Tt) in zip(frames, tgts):
+            Rh, th = se3(oMi[j], M)
+            es.append(ik.log6_mp(mm(tr(Rh), TR), mtv(Rh, [Tt[i] - th[i] for i in range(3)])))
+            J = [[f(0)] * n for _ in range(6)]
+            i = j
+            while i >= 0:  # LOCAL: column = [R_f^T (a x (p_f - o_i)); R_f^T a]
+                a = mv(oMi[i][0], axes[i])
+                lin, ang = mtv(Rh, cross(a, [th[r] - oMi[i][1][r] for r in range(3)])), mtv(Rh, a)
+                for r in range(3):
+                    J[r][i], J[3 + r][i] = lin[r], ang[r]
+                i = model.parent[i]
+            rows += J
+        nL, nR = (mp.sqrt(sum(x * x for x in e)) for e in es)
+        if it >= max_iters or (nL < eps and nR < eps):
+            break
+        Jm = mp.matrix(rows)
+        x = Jm.T * mp.lu_solve(Jm * Jm.T, mp.matrix(es[0] + es[1]))
+        q = [min(max(lo[k], q[k] + x[k] * f(dt)), hi[k]) for k in range(n)]
+    conv = bool(nL < eps and nR < eps) and it < max_iters
+    return np.array([float(v) for v in q]), conv, it, (float(nL), float(nR))

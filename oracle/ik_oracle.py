@@ -281,7 +281,41 @@ def computeqgrasppose(q0, cube_R, cube_t, max_iters=MAX_ITERS, dt=DT, eps=EPSILO
     return q, False, max_iters, (np.linalg.norm(eL), np.linalg.norm(eR))
 
 
-def computeqgrasppose_mp(q0, cube_R, cube_t, dps=32, max_iters=MAX_ITERS, dt=DT, eps=EPSILON):
+def log6_mp(R, p):
+    """pin.log6 of (R, p) given as nested lists of mpmath numbers, at the current mp.dps -> [v; w]
+    (the angle by atan2 of the skew part and the trace: no cancellation)."""
+    import mpmath as mp
+    f = mp.mpf
+    sk = [R[2][1] - R[1][2], R[0][2] - R[2][0], R[1][0] - R[0][1]]
+    s = mp.sqrt(sk[0] ** 2 + sk[1] ** 2 + sk[2] ** 2) / 2
+    c = (R[0][0] + R[1][1] + R[2][2] - 1) / 2
+    th = mp.atan2(s, c)
+    if th >= mp.pi - f("1e-2"):
+        cphi = -c
+        b = th * th / (1 + cphi)
+        w = []
+        for i, (a_, b_) in enumerate(((2, 1), (0, 2), (1, 0))):
+            tmp = (R[i][i] + cphi) * b
+            sg = 1 if R[a_][b_] > R[b_][a_] else -1
+            w.append(sg * (mp.sqrt(tmp) if tmp > 0 else f(0)))
+    else:
+        k = th / (2 * s) if s > 0 else f("0.5")
+        w = [k * x for x in sk]
+    if th < f("1e-5"):
+        # 1 - cos(th) keeps dps - 2 log10(1 / th) digits (none below 1e-16: a
+        # full step at dt = 1 lands there); the series' next terms are th^6 / 30240
+        # and th^4 / 30240, below 1e-24
+        t2 = th * th
+        al, be = 1 - t2 / 12 - t2 * t2 / 720, f(1) / 12 + t2 / 720
+    else:
+        al = th * mp.sin(th) / (2 * (1 - mp.cos(th)))
+        be = 1 / (th * th) - mp.sin(th) / (2 * th * (1 - mp.cos(th)))
+    wp = w[0] * p[0] + w[1] * p[1] + w[2] * p[2]
+    cr = [w[1] * p[2] - w[2] * p[1], w[2] * p[0] - w[0] * p[2], w[0] * p[1] - w[1] * p[0]]
+    return [al * p[i] - cr[i] / 2 + be * wp * w[i] for i in range(3)] + w
+
+
+def computeqgrasppose_mp(q0, cube_R, cube_t, dps=32, max_iters=MAX_ITERS, dt=DT, eps=EPSILON, lam=0.0):
     """The loop of `computeqgrasppose` evaluated in `dps`-digit arithmetic
     (mpmath) from the float64 model constants and inputs, rounded to float64
     only at the end: the mathematically exact answer the float64 loops
@@ -289,7 +323,8 @@ def computeqgrasppose_mp(q0, cube_R, cube_t, dps=32, max_iters=MAX_ITERS, dt=DT,
     approach), the reference's own float64 result carries rounding noise of
     ~1e-8 (its acos((tr-1)/2) near theta ~1e-3 loses ~10 digits), so this, not
     one float64 run, is what "within 1e-9" is measured against
-    (tests/golden/sensitive_cases.npz).  Slow (~0.1 s per update)."""
+    (tests/golden/sensitive_cases.npz).  `lam` as in `computeqgrasppose`.  Slow
+    (~0.1 s per update)."""
     import mpmath as mp
     mp.mp.dps = dps
     f = mp.mpf
@@ -331,31 +366,6 @@ def computeqgrasppose_mp(q0, cube_R, cube_t, dps=32, max_iters=MAX_ITERS, dt=DT,
     tgts = [se3(cube, (mat(H[0]), vec(H[1]))) for H in (HOOK_LEFT, HOOK_RIGHT)]
     lo, hi = [f(float(x)) for x in LOWER], [f(float(x)) for x in UPPER]
 
-    def log6_mp(R, p):
-        sk = [R[2][1] - R[1][2], R[0][2] - R[2][0], R[1][0] - R[0][1]]
-        s = mp.sqrt(sk[0] ** 2 + sk[1] ** 2 + sk[2] ** 2) / 2
-        c = (R[0][0] + R[1][1] + R[2][2] - 1) / 2
-        th = mp.atan2(s, c)
-        if th >= mp.pi - f("1e-2"):
-            cphi = -c
-            b = th * th / (1 + cphi)
-            w = []
-            for i, (a_, b_) in enumerate(((2, 1), (0, 2), (1, 0))):
-                tmp = (R[i][i] + cphi) * b
-                sg = 1 if R[a_][b_] > R[b_][a_] else -1
-                w.append(sg * (mp.sqrt(tmp) if tmp > 0 else f(0)))
-        else:
-            k = th / (2 * s) if s > 0 else f("0.5")
-            w = [k * x for x in sk]
-        if th == 0:
-            al, be = f(1), f(1) / 12
-        else:
-            al = th * mp.sin(th) / (2 * (1 - mp.cos(th)))
-            be = 1 / (th * th) - mp.sin(th) / (2 * th * (1 - mp.cos(th)))
-        wp = w[0] * p[0] + w[1] * p[1] + w[2] * p[2]
-        cr = [w[1] * p[2] - w[2] * p[1], w[2] * p[0] - w[0] * p[2], w[0] * p[1] - w[1] * p[0]]
-        return [al * p[i] - cr[i] / 2 + be * wp * w[i] for i in range(3)] + w
-
     q = [f(float(x)) for x in q0]
     for it in range(max_iters + 1):
         oMi = []
@@ -384,7 +394,7 @@ def computeqgrasppose_mp(q0, cube_R, cube_t, dps=32, max_iters=MAX_ITERS, dt=DT,
             break
         Jm = mp.matrix(Js[0] + Js[1])
         em = mp.matrix(es[0] + es[1])
-        x = Jm.T * mp.lu_solve(Jm * Jm.T, em)
+        x = Jm.T * mp.lu_solve(Jm * Jm.T + f(lam) * mp.eye(12), em)
         q = [min(max(lo[k], q[k] + x[k] * f(dt)), hi[k]) for k in range(NQ)]
     conv = bool(nL < eps and nR < eps) and it < max_iters
     return np.array([float(v) for v in q]), conv, it, (float(nL), float(nR))

@@ -100,10 +100,11 @@ def cpu_threads():
     return n
 
 
-def rounding_envelope(targets, q0, q_ref, conv_ref, iters_ref, flags, runs=4, threads=0):
+def rounding_envelope(targets, q0, q_ref, conv_ref, iters_ref, flags, runs=4, threads=0, **kw):
     """How far the float64 loop's answer moves when its FK rounds differently:
     the C oracle (oracle/ikg_oracle.c) with `flags` | JITTER (every FK rotation
-    entry moved by 0 / +-1 ulp) for `runs` jitter seeds.  Returns (env [B]:
+    entry moved by 0 / +-1 ulp) for `runs` jitter seeds; `kw`: the loop's
+    max_iters, eps and dt where they are not the reference's.  Returns (env [B]:
     the largest |q - q_ref| among runs with the same flag and update count,
     outcomes [B]: the set of (converged, iters) the runs reached)."""
     from oracle import c_oracle
@@ -111,7 +112,7 @@ def rounding_envelope(targets, q0, q_ref, conv_ref, iters_ref, flags, runs=4, th
     env = np.zeros(B)
     outcomes = [{(bool(conv_ref[i]), int(iters_ref[i]))} for i in range(B)]
     for s in range(1, runs + 1):
-        q, c, it, _ = c_oracle.solve_ex(targets, q0, flags | c_oracle.JITTER, seed=s, threads=threads)
+        q, c, it, _ = c_oracle.solve_ex(targets, q0, flags | c_oracle.JITTER, seed=s, threads=threads, **kw)
         same = (c == conv_ref) & (it == iters_ref)
         env = np.maximum(env, np.where(same, np.abs(q - q_ref).max(axis=1), 0.0))
         for i in range(B):
