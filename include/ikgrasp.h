@@ -640,6 +640,76 @@ int ikg_project_paths(const ikg_model* model, int device, const void* q_curr, co
                       int32_t n_geoms, const ikg_params* params, void* robot_path, void* cube_path, int32_t* n_nodes,
                       int32_t* status, void* stream, uint32_t flags);
 
+/* ---- Trajectory check: collision, clearance, grasp and joint limits along curves ----
+ * ikg_trajectory_check_batch samples each of B joint-space Bezier curves at S
+ * times and answers, per sample and folded per curve, what the planner checks
+ * at its vertices only.  fp64.  Per (curve b, sample k):
+ *   t_k   = t_min + k (t_max - t_min) / (S - 1), t_{S-1} = t_max exactly
+ *   q     = the curve at t_k (ikg_bezier_eval_batch's function: two control
+ *           points give mult * P0 at every time)
+ *   cube  = IKG_CUBE_CARRIED: oM(left effector) * hook_left^-1, the placement at
+ *           which the left hand's IK error is zero; IKG_CUBE_FIXED: cube_fixed[b]
+ *   grasp = norm(log6(oMhand^-1 * cube * hook)), the quantity the IK compares
+ *           with eps: the right hand's (CARRIED; the left is zero by construction)
+ *           or the larger of the two hands' (FIXED)
+ *   limit = max(0, max_j(q_j - upper_j), max_j(lower_j - q_j)) (tools.jointlimitscost)
+ *   collision = ikg_collision_batch's answer at (q, cube)
+ *   clearance = ikg_distance_batch's answer at (q, cube) over pair_idx; computed
+ *           only when n_pairs > 0 and a clearance output is requested, else the
+ *           clearance outputs hold 1e30 and arg_clearance -1
+ * Per curve: first_collision (lowest colliding sample, -1 none), first_pair (the
+ * lowest-index colliding scene pair at that sample), n_collision, and the
+ * minimum clearance / maximum grasp / maximum limit with the LOWEST sample among
+ * exact ties.  Every output is optional (NULL).  The per-curve outputs are a
+ * fold of the per-sample values in sample order; no output depends on
+ * samples_per_wave.
+ *   q_curves->points [B, n_points, nq], cube_fixed [B,12] (FIXED), the outputs:
+ *     device arrays, or host arrays with IKG_FLAG_HOST_POINTERS
+ *   pair_idx [n_pairs]: HOST array of scene pair indices (as ikg_distance_batch); may be
+ *     NULL with n_pairs == 0
+ * One 64-lane wave walks samples_per_wave consecutive samples of one curve and
+ * carries the collision witness from one to the next; a second kernel folds the
+ * waves' partial results per curve.  samples_per_wave == 0: the least run that
+ * still gives about 2,048 waves (two rounds of one wave per SIMD), at most S.
+ * A host-pointer call checks finiteness and every limit (S >= 2, n_points 2 .. 64,
+ * t_max > t_min, cube_mode, FIXED with cube_fixed, pair_idx inside the scene's
+ * pairs) and returns IKG_EINVAL before any launch; the limits are checked with
+ * device pointers too.  Needs ikg_model_set_collision with a target geometry.
+ * B == 0 is a no-op.  Stream-ordered; the scratch comes from the model's pool and
+ * the call waits for the stream before it returns (the staged pair list is freed
+ * on return).  Not capturable.
+ */
+#define IKG_CUBE_CARRIED 0
+#define IKG_CUBE_FIXED 1
+typedef struct ikg_trajcheck_params {
+  int32_t samples;          /* S >= 2; 151 */
+  int32_t cube_mode;        /* IKG_CUBE_CARRIED */
+  int32_t samples_per_wave; /* 0 = chosen by the launcher; >= 1 forces it (tests) */
+} ikg_trajcheck_params;
+typedef struct ikg_trajcheck_out { /* every field optional (NULL) */
+  int32_t* first_collision;        /* [B] lowest colliding sample, -1 = none */
+  int32_t* first_pair;             /* [B] lowest-index colliding pair at that sample, -1 = none */
+  int32_t* n_collision;            /* [B] colliding samples */
+  void* min_clearance;
+  int32_t* arg_clearance; /* [B] */
+  void* max_grasp;
+  int32_t* arg_grasp; /* [B] */
+  void* max_limit;
+  int32_t* arg_limit; /* [B] */
+  uint8_t* collision; /* [B,S] */
+  void* clearance;    /* [B,S] */
+  void* grasp;        /* [B,S] */
+  void* limit;        /* [B,S] */
+  void* cube;         /* [B,S,12] the cube placement used at each sample */
+} ikg_trajcheck_out;
+void ikg_trajcheck_params_default(ikg_trajcheck_params* p);
+/* what samples_per_wave == 0 resolves to for B >= 1 curves of `samples` >= 2 samples (0 otherwise) */
+int ikg_trajcheck_samples_per_wave(int64_t B, int32_t samples);
+int ikg_trajectory_check_batch(const ikg_model* model, int device, const ikg_bezier_set* q_curves, int64_t B,
+                               const void* cube_fixed, const int32_t* pair_idx, int32_t n_pairs,
+                               const ikg_trajcheck_params* params, const ikg_trajcheck_out* out, void* stream,
+                               uint32_t flags);
+
 /* Thread-local message of the last failure ("" if none). */
 const char* ikg_last_error(void);
 

@@ -20,6 +20,7 @@
 #include "ikg_fit.hpp"
 #include "ikg_model_build.hpp"
 #include "ikg_planner.hpp"
+#include "ikg_trajcheck.hpp"
 #include "ikgrasp.h"
 
 namespace {
@@ -1692,6 +1693,108 @@ int ikg_project_paths(const ikg_model* model, int device, const void* q_curr, co
   e = ws.release();
   if (e != hipSuccess) return hip_fail(e, "projection workspace free");
   return st.finish();
+}
+
+void ikg_trajcheck_params_default(ikg_trajcheck_params* p) {
+  if (!p) return;
+  p->samples = 151;  // 15 s at 0.1 s: the demo's total_time
+  p->cube_mode = IKG_CUBE_CARRIED;
+  p->samples_per_wave = 0;
+}
+
+int ikg_trajcheck_samples_per_wave(int64_t B, int32_t samples) {
+  if (B < 1 || samples < 2) return 0;
+  return ikg::trajcheck_samples_per_wave(B, samples, 0);
+}
+
+int ikg_trajectory_check_batch(const ikg_model* model, int device, const ikg_bezier_set* q_curves, int64_t B,
+                               const void* cube_fixed, const int32_t* pair_idx, int32_t n_pairs,
+                               const ikg_trajcheck_params* params, const ikg_trajcheck_out* out, void* stream,
+                               uint32_t flags) {
+  g_err[0] = 0;
+  if (!model) return fail(IKG_EINVAL, "model is NULL");
+  if (!params) return fail(IKG_EINVAL, "params is NULL");
+  if (!out) return fail(IKG_EINVAL, "out is NULL");
+  if (B < 0) return fail(IKG_EINVAL, "B must be >= 0");
+  const int S = params->samples;
+  if (S < 2) return fail(IKG_EINVAL, "samples must be >= 2");
+  if (params->samples_per_wave < 0) return fail(IKG_EINVAL, "samples_per_wave must be >= 0");
+  if (params->cube_mode != IKG_CUBE_CARRIED && params->cube_mode != IKG_CUBE_FIXED)
+    return fail(IKG_EINVAL, "cube_mode %d unknown", params->cube_mode);
+  if (params->cube_mode == IKG_CUBE_FIXED && B > 0 && !cube_fixed)
+    return fail(IKG_EINVAL, "IKG_CUBE_FIXED needs cube_fixed");
+  if (n_pairs < 0 || (n_pairs > 0 && !pair_idx)) return fail(IKG_EINVAL, "pair_idx must hold n_pairs >= 0 entries");
+  if (!model->col.present) return fail(IKG_EINVAL, "%s", model->col.missing);
+  if (model->col.k64.target_geom < 0) return fail(IKG_EINVAL, "the collision scene has no target geometry");
+  for (int32_t k = 0; k < n_pairs; ++k)
+    if (pair_idx[k] < 0 || pair_idx[k] >= model->col.k64.n_pairs)
+      return fail(IKG_EINVAL, "pair_idx[%d] = %d outside [0, %d)", k, pair_idx[k], model->col.k64.n_pairs);
+  const int nq = model->desc.nq;
+  if (int rc = check_bezier_set(q_curves, nq, B, flags, "q_curves")) return rc;
+  if (params->cube_mode == IKG_CUBE_FIXED)
+    if (int rc = check_finite_rows<double>(flags, B, {{cube_fixed, 12, "cube_fixed"}})) return rc;
+  const int spw = ikg::trajcheck_samples_per_wave(B > 0 ? B : 1, S, params->samples_per_wave);
+  const int chunks = (S + spw - 1) / spw;
+  if (B * chunks > kMaxWaves || B * (int64_t)S > (int64_t)1 << 40)
+    return fail(IKG_EINVAL, "B=%lld with %d samples is too large for one launch", (long long)B, S);
+  DeviceGuard g(device);
+  if (g.rc) return g.rc;
+  if (B == 0) return IKG_OK;
+  ikg_model* m = const_cast<ikg_model*>(model);
+  hipStream_t s = (hipStream_t)stream;
+  if (ikg::stream_capturing(s)) return fail(IKG_EINVAL, "ikg_trajectory_check_batch is not capturable");
+  ikg::ws_drain(&m->ws);
+  const ikg::KModel<double>* dm = nullptr;
+  const ikg::KCollision<double>* dc = nullptr;
+  int rc = m->kin.get<double>(m->mu, device, &dm);
+  if (rc || (rc = m->col.get<double>(m->mu, device, &dc))) return rc;
+  const bool want_clearance = n_pairs > 0 && (out->min_clearance || out->arg_clearance || out->clearance);
+  Staging st(s, flags);
+  ikg::TrajCheckArgs a{};
+  a.points = (const double*)st.in(q_curves->points, sizeof(double) * q_curves->n_points * nq * B);
+  a.n_points = q_curves->n_points;
+  a.t_min = q_curves->t_min;
+  a.t_max = q_curves->t_max;
+  a.mult = q_curves->mult;
+  a.S = S;
+  a.spw = spw;
+  a.chunks = chunks;
+  a.cube_mode = params->cube_mode;
+  a.cube_fixed = a.cube_mode == IKG_CUBE_FIXED ? (const double*)st.in(cube_fixed, sizeof(double) * 12 * B) : nullptr;
+  a.n_idx = want_clearance ? n_pairs : 0;
+  a.pair_idx = want_clearance ? (const int32_t*)st.upload(pair_idx, sizeof(int32_t) * n_pairs) : nullptr;
+  const size_t rows = (size_t)B * S;
+  a.collision = (uint8_t*)st.out(out->collision, rows);
+  a.clearance = (double*)st.out(out->clearance, sizeof(double) * rows);
+  a.grasp = (double*)st.out(out->grasp, sizeof(double) * rows);
+  a.limit = (double*)st.out(out->limit, sizeof(double) * rows);
+  a.cube = (double*)st.out(out->cube, sizeof(double) * 12 * rows);
+  ikg::TrajFoldOut o{};
+  o.first_collision = (int32_t*)st.out(out->first_collision, sizeof(int32_t) * B);
+  o.first_pair = (int32_t*)st.out(out->first_pair, sizeof(int32_t) * B);
+  o.n_collision = (int32_t*)st.out(out->n_collision, sizeof(int32_t) * B);
+  o.min_clearance = (double*)st.out(out->min_clearance, sizeof(double) * B);
+  o.arg_clearance = (int32_t*)st.out(out->arg_clearance, sizeof(int32_t) * B);
+  o.max_grasp = (double*)st.out(out->max_grasp, sizeof(double) * B);
+  o.arg_grasp = (int32_t*)st.out(out->arg_grasp, sizeof(int32_t) * B);
+  o.max_limit = (double*)st.out(out->max_limit, sizeof(double) * B);
+  o.arg_limit = (int32_t*)st.out(out->arg_limit, sizeof(int32_t) * B);
+  if (st.rc) return st.rc;
+  // scratch: the binomial factors, then one partial per wave
+  double bc[ikg::kMaxBezier] = {};
+  ikg::bezier_coeffs(a.n_points, bc);
+  const size_t bc_bytes = sizeof(double) * ikg::kMaxBezier;
+  rc = with_scratch(m, bc_bytes + sizeof(ikg::TrajPartial) * (size_t)B * chunks, s, "trajectory check",
+                    [&](void* ws, const char*& what) {
+                      what = "trajectory check table upload";
+                      const hipError_t e = ikg::launch_table_write((double*)ws, bc, ikg::kMaxBezier, s);
+                      if (e != hipSuccess) return e;
+                      a.bc = (const double*)ws;
+                      a.part = (ikg::TrajPartial*)((char*)ws + bc_bytes);
+                      what = "ikg trajectory check kernel launch";
+                      return ikg::launch_trajcheck(dm, dc, a, B, o, s);
+                    });
+  return rc ? rc : st.finish(true);  // the staged pair list is freed on return
 }
 
 }  // extern "C"

@@ -10,6 +10,9 @@
 //    until a collision-free one or max_iters.  One wave per problem: lanes 0/1
 //    run the pair iteration (ikg_device.hpp stages), all 64 lanes share the
 //    ~745-pair check.
+//  * ikg_trajcheck_kernel: collision, clearance, grasp error and joint limits at
+//    consecutive samples of a Bezier curve, one wave per run of samples with the
+//    witness carried along (ikg_trajectory_check_batch; ikg_trajcheck.hpp).
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -20,6 +23,7 @@
 #include "ikg_device.hpp"
 #include "ikg_launch.hpp"
 #include "ikg_solve.hpp"
+#include "ikg_trajcheck.hpp"
 
 namespace ikg {
 
@@ -230,6 +234,36 @@ __global__ __launch_bounds__(64) void ikg_collision_kernel(const KModel<T>* __re
 }
 
 // ---------------------------------------------------------------- planner queries
+// ikg_distance_kernel's minimum for the trajectory check's wave: pair_distance
+// over pair_idx at the geometry placements S.P, the pairs strided over the 64
+// lanes, every lane returning the wave's minimum.  The same statements as the
+// kernel below keeps inline: calling this from ikg_distance_kernel changed that
+// kernel's register allocation (166 -> 248 VGPRs, 3 -> 1 waves per SIMD), so
+// the kernel's body stays as it was and the two are held together by
+// tests/test_gpu_trajcheck.py's composed route (equal clearances).
+template <typename T>
+__device__ inline double distance_wave(const KCollision<T>* __restrict__ c, const CollideScratch<T>& S,
+                                       const int32_t* __restrict__ pair_idx, int n_idx) {
+  const int lane = threadIdx.x & 63;
+  double d = 1e30;
+  for (int k = lane; k < n_idx; k += 64) {
+    const int pr = pair_idx[k];
+    double P2[2][12], D2[2][3];
+    int K2[2];
+    for (int h = 0; h < 2; ++h) {
+      const int g = c->pairs[pr][h];
+      for (int i = 0; i < 12; ++i) P2[h][i] = (double)S.P[g][i];
+      for (int i = 0; i < 3; ++i) D2[h][i] = (double)c->dims[g][i];
+      K2[h] = c->kind[g];
+    }
+    const Shape<double> A{P2[0], P2[0] + 9, D2[0], K2[0]}, Bs{P2[1], P2[1] + 9, D2[1], K2[1]};
+    d = fmin(d, pair_distance(A, Bs));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) d = fmin(d, __shfl_xor(d, off));
+  return d;
+}
+
 // distanceToObstacle (tools.py:37-51): min over the given active pairs of the
 // pair distance at configuration q, one wave per configuration.
 template <typename T>
@@ -321,6 +355,104 @@ template hipError_t launch_target_env<double>(const KCollision<double>*, const v
                                               uint8_t*, hipStream_t);
 template hipError_t launch_target_env<float>(const KCollision<float>*, const void*, int64_t, const int32_t*, int,
                                              uint8_t*, hipStream_t);
+
+// ---------------------------------------------------------------- trajectory check
+// ikg_trajectory_check_batch: one wave walks a.spw consecutive samples of one
+// curve (block = curve * a.chunks + chunk).  Per sample: the curve's value
+// (bezier_eval, one lane per joint), the frames as ikg_collision_kernel stages
+// them, the cube placement and the grasp error from the effector frames, the
+// joint-limit excess, collide_wave with the witness carried from the sample
+// before (-1 at the start of the run) and, where asked for, ikg_distance_kernel's
+// minimum over pair_idx.  Lane 0 folds the samples into the wave's partial.
+__global__ __launch_bounds__(64) void ikg_trajcheck_kernel(const KModel<double>* __restrict__ m,
+                                                           const KCollision<double>* __restrict__ c,
+                                                           const TrajCheckArgs a) {
+  using T = double;
+  __shared__ CollideScratch<T> S;
+  __shared__ T tgt[12];
+  __shared__ T eff[2][12];
+  __shared__ T gn[2];
+  __shared__ Witness<T> W;
+  const int lane = threadIdx.x;
+  const int nq = m->nq;
+  const int64_t b = blockIdx.x / a.chunks;
+  const int ch = (int)(blockIdx.x % a.chunks);
+  const int k0 = ch * a.spw, k1 = min(a.S, k0 + a.spw);
+  const KBezier<T> kb{a.points + b * a.n_points * nq, a.bc, a.n_points, nq, a.t_min, a.t_max, a.mult};
+  const bool fixed = a.cube_mode == kCubeFixed;
+  if (lane == 0) {
+    W.pair = -1;
+    W.cert_ok = 0;
+  }
+  TrajPartial part;
+  partial_init(part);
+  for (int k = k0; k < k1; ++k) {
+    const int64_t row = b * a.S + k;
+    if (lane < nq) S.q[lane] = bezier_eval(kb, trajcheck_time(a.t_min, a.t_max, a.S, k), lane);
+    if (fixed && lane < 12) tgt[lane] = a.cube_fixed[b * 12 + lane];
+    __syncthreads();
+    stage_trig_par(m, S);
+    __syncthreads();
+    // the frames are needed before the check, for the cube it is run with; collide_wave forms them
+    // again from the same S.sn / S.cs (it is shared with the other check kernels and stays as it is)
+    if (lane < nq) joint_local(m, lane, S.sn[lane], S.cs[lane], S.L[lane]);
+    __syncthreads();
+    if (lane < nq) joint_world(S.par, lane, S.L, S.F[lane]);
+    __syncthreads();
+    if (lane < 2) effector_world(m, lane, S.F, eff[lane]);
+    __syncthreads();
+    if (!fixed && lane == 0) carried_cube(m, eff[0], tgt);
+    __syncthreads();
+    // CARRIED: the left hand's error is zero by construction and is not computed
+    if (lane < 2) gn[lane] = (fixed || lane == 1) ? grasp_norm(m, lane, eff[lane], tgt) : T(0);
+    T lim = lane < nq ? limit_excess(m, lane, S.q[lane]) : T(0);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) lim = fmax(lim, __shfl_xor(lim, off));
+    const bool col = collide_wave<T, true>(m, c, S, tgt, W);
+    __syncthreads();  // W.pair and gn (lane 0 / 1) are visible; S.F is this sample's
+    const bool want_d = a.n_idx > 0;
+    double d = kNoClearance;
+    if (want_d) {
+      // collide_wave leaves S.P partly filled when its witness answered and does not say which way it
+      // went: the placements are formed again for every sample (n_geoms matrix products over 64 lanes)
+      for (int g = lane; g < c->n_geoms; g += 64) geom_world(c, g, S.F, tgt, S.P[g]);
+      __syncthreads();
+      d = distance_wave(c, S, a.pair_idx, a.n_idx);
+    }
+    const T grasp = fixed ? fmax(gn[0], gn[1]) : gn[1];
+    if (lane == 0) {
+      partial_add(part, k, col, col ? W.pair : -1, want_d, d, grasp, lim);
+      if (a.collision) a.collision[row] = col ? 1 : 0;
+      if (a.clearance) a.clearance[row] = d;
+      if (a.grasp) a.grasp[row] = grasp;
+      if (a.limit) a.limit[row] = lim;
+    }
+    if (a.cube && lane < 12) a.cube[row * 12 + lane] = tgt[lane];
+    __syncthreads();  // before the next sample rewrites S, tgt, eff and gn
+  }
+  if (lane == 0) a.part[blockIdx.x] = part;
+}
+
+// The waves' partials of each curve folded in sample order, one lane per curve.
+__global__ __launch_bounds__(256) void ikg_trajcheck_fold_kernel(const TrajPartial* __restrict__ part, int chunks,
+                                                                 int64_t B, const TrajFoldOut o) {
+  const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  TrajPartial acc = part[b * chunks];
+  for (int ch = 1; ch < chunks; ++ch) partial_merge(acc, part[b * chunks + ch]);
+  fold_store(o, b, acc);
+}
+
+hipError_t launch_trajcheck(const KModel<double>* dm, const KCollision<double>* dc, const TrajCheckArgs& a, int64_t B,
+                            const TrajFoldOut& o, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  hipLaunchKernelGGL(ikg_trajcheck_kernel, dim3((unsigned)(B * a.chunks)), dim3(64), 0, s, dm, dc, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(ikg_trajcheck_fold_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, a.part, a.chunks, B,
+                     o);
+  return hipGetLastError();
+}
 
 // ---------------------------------------------------------------- continuation
 // G problems per wave (LG = 64/G lanes each).  Per-problem state lives in a

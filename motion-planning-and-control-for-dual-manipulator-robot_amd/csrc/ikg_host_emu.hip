@@ -22,6 +22,7 @@ thread_local bool ikg_emu_small_angle = false;
 #include "ikg_fit.hpp"
 #include "ikg_model_build.hpp"
 #include "ikg_planner.hpp"
+#include "ikg_trajcheck.hpp"
 #include "ikgrasp.h"
 
 namespace {
@@ -1017,4 +1018,87 @@ extern "C" int ikg_emu_project_paths(const ikg_model_desc* d, const ikg_collisio
     if (steps_run) *steps_run = (int32_t)step;
   }
   return chest_mismatch ? -3 : 0;
+}
+
+// ---------------------------------------------------------------- trajectory check on the CPU
+// ikg_trajectory_check_batch with host pointers: per sample the functions of
+// ikg_trajcheck.hpp, the check stages run serially (emu_collide's, with the
+// lowest colliding pair kept) and pair_distance over pair_idx as
+// ikg_distance_kernel forms it, then partial_add over the samples in order
+// (what the waves' partials fold to whatever the chunking).  -1 where the entry
+// returns IKG_EINVAL.  tests/test_trajcheck.py.
+extern "C" int ikg_emu_trajectory_check(const ikg_model_desc* d, const ikg_collision_desc* cd,
+                                        const ikg_bezier_set* curves, int64_t B, const double* cube_fixed,
+                                        const int32_t* pair_idx, int32_t n_pairs, const ikg_trajcheck_params* p,
+                                        const ikg_trajcheck_out* out) {
+  using namespace ikg;
+  if (!d || !cd || !curves || !p || !out || B < 0) return -1;
+  const ikg_bezier one{(const double*)curves->points, curves->n_points, curves->t_min, curves->t_max, curves->mult};
+  if (B > 0 && !emu_curve_ok(&one)) return -1;
+  if (curves->n_points < 2 || curves->n_points > kMaxBezier || !(curves->t_max > curves->t_min)) return -1;
+  if (p->samples < 2 || p->samples_per_wave < 0) return -1;
+  if (p->cube_mode != IKG_CUBE_CARRIED && p->cube_mode != IKG_CUBE_FIXED) return -1;
+  if (p->cube_mode == IKG_CUBE_FIXED && B > 0 && !cube_fixed) return -1;
+  if (n_pairs < 0 || (n_pairs > 0 && !pair_idx)) return -1;
+  KModel<double> m;
+  build_kmodel<double>(*d, m);
+  static thread_local KCollision<double> kc;
+  build_kcollision<double>(*cd, kc);
+  if (kc.target_geom < 0) return -1;
+  for (int32_t k = 0; k < n_pairs; ++k)
+    if (pair_idx[k] < 0 || pair_idx[k] >= kc.n_pairs) return -1;
+  const int nq = d->nq, S = p->samples, n = curves->n_points;
+  const bool fixed = p->cube_mode == IKG_CUBE_FIXED;
+  const bool want_d = n_pairs > 0 && (out->min_clearance || out->arg_clearance || out->clearance);
+  double bc[kMaxBezier];
+  bezier_coeffs(n, bc);
+  const TrajFoldOut o{out->first_collision,        out->first_pair,    out->n_collision,
+                      (double*)out->min_clearance, out->arg_clearance, (double*)out->max_grasp,
+                      out->arg_grasp,              (double*)out->max_limit, out->arg_limit};
+  for (int64_t b = 0; b < B; ++b) {
+    const KBezier<double> kb{(const double*)curves->points + b * n * nq, bc, n, nq, curves->t_min, curves->t_max,
+                             curves->mult};
+    TrajPartial part;
+    partial_init(part);
+    for (int k = 0; k < S; ++k) {
+      const int64_t row = b * S + k;
+      double q[kMaxNq], L[kMaxNq][12], F[kMaxNq][12], P[kMaxGeoms][12], eff[2][12], tgt[12];
+      const double t = trajcheck_time(curves->t_min, curves->t_max, S, k);
+      double lim = 0.0;
+      for (int j = 0; j < nq; ++j) {
+        q[j] = bezier_eval(kb, t, j);
+        double sn, cs;
+        Prec<double>::sincos_(q[j], &sn, &cs);
+        joint_local(&m, j, sn, cs, L[j]);
+        lim = fmax(lim, limit_excess(&m, j, q[j]));
+      }
+      for (int j = 0; j < nq; ++j) joint_world(m.jparent, j, L, F[j]);
+      for (int h = 0; h < 2; ++h) effector_world(&m, h, F, eff[h]);
+      if (fixed)
+        for (int i = 0; i < 12; ++i) tgt[i] = cube_fixed[b * 12 + i];
+      else
+        carried_cube(&m, eff[0], tgt);
+      const double gR = grasp_norm(&m, 1, eff[1], tgt);
+      const double grasp = fixed ? fmax(grasp_norm(&m, 0, eff[0], tgt), gR) : gR;
+      for (int g = 0; g < kc.n_geoms; ++g) geom_world(&kc, g, F, tgt, P[g]);
+      int pair = -1;
+      for (int i = 0; i < kc.n_pairs && pair < 0; ++i)
+        if (pair_hit(&kc, i, P)) pair = i;
+      double dmin = kNoClearance;
+      if (want_d)
+        for (int i = 0; i < n_pairs; ++i) {
+          const int ga = kc.pairs[pair_idx[i]][0], gb = kc.pairs[pair_idx[i]][1];
+          dmin = fmin(dmin, pair_distance(pair_shape(&kc, ga, P), pair_shape(&kc, gb, P)));
+        }
+      partial_add(part, k, pair >= 0, pair, want_d, dmin, grasp, lim);
+      if (out->collision) out->collision[row] = pair >= 0 ? 1 : 0;
+      if (out->clearance) ((double*)out->clearance)[row] = dmin;
+      if (out->grasp) ((double*)out->grasp)[row] = grasp;
+      if (out->limit) ((double*)out->limit)[row] = lim;
+      if (out->cube)
+        for (int i = 0; i < 12; ++i) ((double*)out->cube)[row * 12 + i] = tgt[i];
+    }
+    fold_store(o, b, part);
+  }
+  return 0;
 }

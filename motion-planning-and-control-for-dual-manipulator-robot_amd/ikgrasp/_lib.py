@@ -138,6 +138,24 @@ class FitParams(C.Structure):
     _fields_ = [("degree", C.c_int32), ("ridge", C.c_double), ("total_time", C.c_double)]
 
 
+class TrajCheckParams(C.Structure):
+    """ikg_trajcheck_params: samples per curve, cube mode, samples per wave (0 = the launcher's choice)."""
+    _fields_ = [("samples", C.c_int32), ("cube_mode", C.c_int32), ("samples_per_wave", C.c_int32)]
+
+
+TRAJCHECK_CURVE = (("first_collision", np.int32), ("first_pair", np.int32), ("n_collision", np.int32),
+                   ("min_clearance", np.float64), ("arg_clearance", np.int32), ("max_grasp", np.float64),
+                   ("arg_grasp", np.int32), ("max_limit", np.float64), ("arg_limit", np.int32))
+TRAJCHECK_SAMPLE = (("collision", np.uint8, ()), ("clearance", np.float64, ()), ("grasp", np.float64, ()),
+                    ("limit", np.float64, ()), ("cube", np.float64, (12,)))
+CUBE_CARRIED, CUBE_FIXED = 0, 1
+
+
+class TrajCheckOut(C.Structure):
+    """ikg_trajcheck_out: optional output pointers, per curve [B] then per sample [B,S]."""
+    _fields_ = [(f[0], C.c_void_p) for f in TRAJCHECK_CURVE + TRAJCHECK_SAMPLE]
+
+
 EXPORTS = [
     "ikg_model_create", "ikg_model_destroy", "ikg_params_default", "ikg_solve_batch",
     "ikg_solve_multistart", "ikg_fk_batch", "ikg_log6_batch", "ikg_last_error", "ikg_version",
@@ -147,6 +165,7 @@ EXPORTS = [
     "ikg_forward_dynamics_batch", "ikg_bezier_eval_batch", "ikg_rollout_params_default", "ikg_control_rollout",
     "ikg_control_rollout_curves", "ikg_fit_params_default", "ikg_bezier_fit_batch",
     "ikg_se3_interpolate_batch", "ikg_nearest_batch", "ikg_project_paths",
+    "ikg_trajcheck_params_default", "ikg_trajectory_check_batch", "ikg_trajcheck_samples_per_wave",
 ]
 
 _lib = None
@@ -244,6 +263,13 @@ def load() -> C.CDLL:
     lib.ikg_project_paths.argtypes = [vp, i32, vp, vp, vp, i64, C.c_double, C.c_int32, vp, C.c_int32,
                                       C.POINTER(Params), vp, vp, vp, vp, vp, C.c_uint32]
     lib.ikg_project_paths.restype = i32
+    lib.ikg_trajcheck_params_default.argtypes = [C.POINTER(TrajCheckParams)]
+    lib.ikg_trajcheck_params_default.restype = None
+    lib.ikg_trajectory_check_batch.argtypes = [vp, i32, C.POINTER(BezierSet), i64, vp, vp, C.c_int32,
+                                               C.POINTER(TrajCheckParams), C.POINTER(TrajCheckOut), vp, C.c_uint32]
+    lib.ikg_trajectory_check_batch.restype = i32
+    lib.ikg_trajcheck_samples_per_wave.argtypes = [i64, C.c_int32]
+    lib.ikg_trajcheck_samples_per_wave.restype = i32
     lib.ikg_model_specialize.argtypes = [vp, i32, i32, C.c_uint32]
     lib.ikg_model_specialize.restype = i32
     lib.ikg_model_is_specialized.argtypes = [vp, i32, i32]
@@ -367,6 +393,13 @@ def fit_params(degree=20, ridge=0.0, total_time=1.0) -> FitParams:
     p = FitParams()
     load().ikg_fit_params_default(C.byref(p))
     p.degree, p.ridge, p.total_time = int(degree), float(ridge), float(total_time)
+    return p
+
+
+def trajcheck_params(samples=151, cube_mode=CUBE_CARRIED, samples_per_wave=0) -> TrajCheckParams:
+    p = TrajCheckParams()
+    load().ikg_trajcheck_params_default(C.byref(p))
+    p.samples, p.cube_mode, p.samples_per_wave = int(samples), int(cube_mode), int(samples_per_wave)
     return p
 
 

@@ -23,7 +23,9 @@ operational-space inertia, the unconstrained QP and the torque line) through
 `ikg_control_torque_batch`.  `controllaw` is the drop-in for the reference
 function.  `maketraj` is the drop-in for the reference's trajectory fit
 (control.py:63-197) and `maketraj_batch` fits B paths in one launch of
-`ikg_bezier_fit_batch`; `save_trajectory` writes the reference's file.  `rollout` runs B closed loops of that law against a free-space
+`ikg_bezier_fit_batch`; `save_trajectory` writes the reference's file.  `checktraj`
+samples fitted curves for collision, clearance, grasp error and joint limits
+in one launch of `ikg_trajectory_check_batch`.  `rollout` runs B closed loops of that law against a free-space
 rigid-body plant in one call of `ikg_control_rollout` (desired state from the
 Bezier curves, torque law, forward dynamics, semi-implicit Euler), and
 `Simulation` is the same plant one tick at a time behind the simulator's
@@ -196,6 +198,10 @@ class FittedTrajectories:
         q_of_t = Curve(list(self.points[i]), self.t_min, self.t_max)
         return q_of_t, q_of_t.derivative(1), q_of_t.derivative(2)
 
+    def check(self, robot, **kw):
+        """`checktraj(robot, self, **kw)`: one verdict per fitted curve."""
+        return checktraj(robot, self, **kw)
+
 
 def maketraj_batch(q0s, q1s, paths, total_time, degree=20, ridge=None, solver=None):
     """The reference's maketraj (control.py:63-197) for B paths in one launch of
@@ -241,6 +247,42 @@ def maketraj(q0, q1, path_points, total_time, ridge=None, solver=None):
     trajectory2.json side effect are not reproduced (`save_trajectory`)."""
     fitted = maketraj_batch([q0], [q1], [path_points], total_time, degree=20, ridge=ridge, solver=solver)
     return list(fitted.curves(0)), bool(fitted.ok[0])
+
+
+def trajectory_ok(report, min_clearance=0.0, max_grasp=None):
+    """The verdict of a trajectory-check report (numpy arrays [B]): no colliding
+    sample, every sample inside the joint limits, the clearance to the obstacle
+    pairs never below `min_clearance` (where a clearance was computed:
+    arg_clearance >= 0) and, when `max_grasp` is given, the grasp error never
+    above it -> bool [B]."""
+    ok = (np.asarray(report["first_collision"]) < 0) & (np.asarray(report["max_limit"]) == 0.0)
+    measured = np.asarray(report["arg_clearance"]) >= 0
+    ok &= ~measured | (np.asarray(report["min_clearance"]) >= min_clearance)
+    if max_grasp is not None:
+        ok &= np.asarray(report["max_grasp"]) <= max_grasp
+    return ok
+
+
+def checktraj(robot, trajs, samples=151, cube="carried", min_clearance=0.0, max_grasp=None, per_sample=False, **kw):
+    """What the planner checks at its vertices only, along whole curves: each
+    curve is sampled at `samples` times in one launch of
+    `ikg_trajectory_check_batch` (GPU, fp64) for collision (the cube carried by
+    the left hand, or at fixed placements), clearance to the obstacle pairs,
+    the grasp error the IK compares with EPSILON and the joint limits.
+    trajs: one (q_of_t, vq_of_t, vvq_of_t) tuple as `maketraj` returns, a
+    `Curve`, or a `FittedTrajectories`.  -> the report of
+    `IKSolver.check_curves` plus ok [B] (`trajectory_ok`).  `kw`: pair_idx,
+    samples_per_wave."""
+    if isinstance(trajs, FittedTrajectories):
+        points, t_min, t_max, mult = np.asarray(trajs.points, dtype=np.float64), trajs.t_min, trajs.t_max, 1.0
+    else:
+        q_of_t = trajs if hasattr(trajs, "control_points_") else trajs[0]
+        pts, t_min, t_max, mult = _lib.curve(q_of_t)
+        points = pts[None]
+    report = robot.solver.check_curves(points, t_min, t_max, mult=mult, samples=samples, cube=cube,
+                                       per_sample=per_sample, **kw)
+    report["ok"] = trajectory_ok(report, min_clearance, max_grasp)
+    return report
 
 
 def rollout(robot, q0, vq0, trajs, t0=None, ticks=1500, **kw):

@@ -30,6 +30,11 @@ order); `computepaths` runs P planners in lock-step, each with its own
 numpy Generator, the trees in device tensors.  Both drive `rrt_iteration`,
 one RRT-Connect iteration whose nearest-neighbour query, projection and
 connect distance are callables (the GPU's here, replayed ones in the CPU tests).
+
+    report = checkpath(robot, path, per_segment=8)
+
+checks what the planner does not: the straight joint-space segments between
+the path's vertices, the connect jump included (ikg_trajectory_check_batch).
 """
 from __future__ import annotations
 
@@ -522,3 +527,82 @@ def computepaths(robot, qinits, qgoals, cube_q0s, cube_goals, seeds, *, max_iter
     paths = rrt_connect(trees, sample, *_gpu_queries(robot, trees, step_size, max_nodes=rows),
                         max_iterations=max_iterations, max_retries=max_retries, goal_tolerance=goal_tolerance)
     return (paths, [trees.export(p) for p in range(P)]) if return_trees else paths
+
+
+# ---------------------------------------------------------------- path check
+def polyline_curves(path):
+    """A path's straight segments as degree-2 Bezier curves -> (points
+    [n_seg,3,nq], rows [n_seg+1,nq]).  Consecutive equal rows are dropped first;
+    segment i has the control points q_i, (q_i + q_{i+1}) / 2, q_{i+1}, which is
+    the straight line (a two-point curve is constant under the reference's
+    Bezier semantics)."""
+    rows = np.asarray(path, dtype=np.float64)
+    if rows.ndim != 2 or len(rows) < 1:
+        raise ValueError(f"a path is [n, nq], got {list(rows.shape)}")
+    keep = np.ones(len(rows), dtype=bool)
+    keep[1:] = np.any(rows[1:] != rows[:-1], axis=1)
+    rows = rows[keep]
+    a, b = rows[:-1], rows[1:]
+    return np.stack([a, (a + b) / 2, b], axis=1), rows
+
+
+def fold_segments(report, per_segment):
+    """Per-segment reports with their per-sample arrays ([n_seg] and [n_seg,
+    per_segment + 1], `IKSolver.check_curves(per_sample=True)`) -> one report of
+    the whole path.  Sample k of segment i is path sample i * per_segment + k; a
+    segment's last sample is the next one's first and is counted once, with the
+    next segment (the last segment keeps its own).  Ties of an extreme go to the
+    lowest path sample.  Adds `segment`, the segment of the first collision (-1
+    = none), and `n_samples`."""
+    ps = int(per_segment)
+    col = np.asarray(report["collision"]).astype(bool)
+    n_seg = col.shape[0]
+    if n_seg == 0:
+        raise ValueError("no segment to fold")
+    own = np.ones((n_seg, ps + 1), dtype=bool)
+    own[:-1, ps] = False
+
+    def along(x):
+        return np.asarray(x)[own]
+
+    c = along(col)
+    out = {"n_samples": int(c.size), "n_collision": int(c.sum()), "first_collision": -1, "first_pair": -1,
+           "segment": -1}
+    if c.any():
+        k = int(np.argmax(c))
+        seg = min(k // ps, n_seg - 1)
+        out["first_collision"], out["segment"] = k, seg
+        # the first colliding sample the fold sees in a segment is that segment's own first
+        if int(np.asarray(report["first_collision"])[seg]) == k - seg * ps:
+            out["first_pair"] = int(np.asarray(report["first_pair"])[seg])
+    measured = bool(np.all(np.asarray(report["arg_clearance"]) >= 0))
+    for name, key, pick in (("clearance", "min_clearance", np.argmin), ("grasp", "max_grasp", np.argmax),
+                            ("limit", "max_limit", np.argmax)):
+        x = along(report[name])
+        k = int(pick(x))
+        skip = name == "clearance" and not measured
+        out[key] = float(x[k])
+        out["arg_" + name] = -1 if skip else k
+    for name in ("collision", "clearance", "grasp", "limit"):
+        out[name] = along(report[name])
+    return out
+
+
+def checkpath(robot, path, per_segment=8, cube="carried", min_clearance=0.0, max_grasp=None, **kw):
+    """A `computepath` result checked as the polyline the planner assumed, the
+    connect jump included: every segment is sampled at per_segment + 1 points
+    in one launch (`IKSolver.check_curves`) and the segments' reports are folded
+    into one (`fold_segments`), sample indices counted along the path.  -> that
+    report plus ok (`ikgrasp.control.trajectory_ok`).  `kw`: pair_idx,
+    samples_per_wave."""
+    from .control import trajectory_ok
+    points, rows = polyline_curves(path)
+    if len(points) == 0:
+        raise ValueError("the path holds one configuration: nothing between vertices to check")
+    rep = robot.solver.check_curves(points, 0.0, 1.0, samples=int(per_segment) + 1, cube=cube, per_sample=True, **kw)
+    host = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in rep.items()}
+    out = fold_segments(host, per_segment)
+    one = {k: np.asarray([out[k]]) for k in ("first_collision", "max_limit", "arg_clearance", "min_clearance",
+                                             "max_grasp")}
+    out["ok"] = bool(trajectory_ok(one, min_clearance, max_grasp)[0])
+    return out

@@ -391,6 +391,60 @@ class IKSolver:
                                               ptr(res["cube_path"]), ptr(res["n_nodes"]), ptr(res["status"]), s, flags))
         return res
 
+    # ------------------------------------------------------------------ trajectory check (fp64)
+    def check_curves(self, points, t_min, t_max, mult=1.0, samples=151, cube="carried", pair_idx=None,
+                     per_sample=False, samples_per_wave=0, stream=None) -> dict:
+        """ikg_trajectory_check_batch: B joint-space Bezier curves sampled at
+        `samples` times each, one verdict per curve.  points [B, n_points, nq]
+        (numpy, or a float64 ROCm tensor); cube "carried" (the placement at
+        which the left hand's grasp error is zero) or fixed placements [B,12]
+        (one row is broadcast).  pair_idx: the scene pairs of the clearance
+        (None = scene.obstacle_pairs(); empty = no clearance).  -> dict of
+        first_collision, first_pair, n_collision, min_clearance, arg_clearance,
+        max_grasp, arg_grasp, max_limit, arg_limit [B]; with per_sample also
+        collision, clearance, grasp, limit [B,S] and cube [B,S,12]."""
+        if self.scene is None:
+            raise RuntimeError("check_curves needs a collision scene (set_collision)")
+        if not _is_torch(points):
+            points = np.asarray(points, dtype=np.float64)
+        if points.ndim != 3 or points.shape[2] != self.nq:
+            raise ValueError(f"points must be [B, n_points, {self.nq}], got {list(points.shape)}")
+        B, n_points = int(points.shape[0]), int(points.shape[1])
+        S = int(samples)
+        prep, empty, ptr, s, device, flags = self._f64_io(points, stream)
+        flat = prep(points, n_points * self.nq)
+        fixed = None
+        if not isinstance(cube, str):
+            if _is_torch(points) != _is_torch(cube):
+                raise ValueError("fixed cube placements must be the same kind of array as points "
+                                 "(numpy, or a float64 tensor on the points' device)")
+            fixed = prep(cube, 12)
+            if fixed.shape[0] == 1 and B != 1:
+                fixed = fixed.expand(B, 12).contiguous() if _is_torch(fixed) else np.ascontiguousarray(
+                    np.broadcast_to(fixed, (B, 12)))
+            if fixed.shape[0] != B:
+                raise ValueError(f"cube has {fixed.shape[0]} placements, points hold {B} curves")
+        elif cube != "carried":
+            raise ValueError(f"cube must be 'carried' or placements [B,12], got {cube!r}")
+        idx = np.ascontiguousarray(self.scene.obstacle_pairs() if pair_idx is None else pair_idx,
+                                   dtype=np.int32).reshape(-1)
+        prm = _lib.trajcheck_params(S, _lib.CUBE_CARRIED if fixed is None else _lib.CUBE_FIXED, samples_per_wave)
+        if _is_torch(points):
+            import torch
+            kinds = {np.int32: torch.int32, np.float64: torch.float64, np.uint8: torch.uint8}
+            alloc = lambda t, *shape: torch.empty(shape, dtype=kinds[t], device=points.device)
+        else:
+            alloc = lambda t, *shape: np.empty(shape, dtype=t)
+        res = {name: alloc(t, B) for name, t in _lib.TRAJCHECK_CURVE}
+        if per_sample:
+            res.update({name: alloc(t, B, S, *tail) for name, t, tail in _lib.TRAJCHECK_SAMPLE})
+        bset = _lib.BezierSet(ptr(flat), n_points, float(t_min), float(t_max), float(mult))
+        out = _lib.TrajCheckOut(*[ptr(res.get(f[0])) for f in _lib.TRAJCHECK_CURVE + _lib.TRAJCHECK_SAMPLE])
+        _lib.check(self.lib.ikg_trajectory_check_batch(self._h, device, C.byref(bset), B, ptr(fixed),
+                                                       idx.ctypes.data if idx.size else None, idx.size, C.byref(prm),
+                                                       C.byref(out), s, flags))
+        return res
+
     # ------------------------------------------------------------------ log6
     def log6(self, M, dtype="f64") -> np.ndarray:
         """pin.log6 of placements [B,12] -> [B,6] ([v; w])."""
