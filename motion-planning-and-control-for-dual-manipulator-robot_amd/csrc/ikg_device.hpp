@@ -2406,6 +2406,41 @@ IKG_HD inline void arm_update(const KModel<typename LaneT<T>::E>* __restrict__ m
   }
 }
 
+// arm_update's `lim` path stage by stage, for the record-free frame-1 fp64 pair loop (MED = false;
+// DESIGN.md §3a.12): all seven integrates, then all seven maxima, then all seven minima, in place
+// of seven integrate -> max -> min chains.  The same expression trees (the same operands in the
+// same order: the same bits); a fence between the stages keeps the machine scheduler from folding
+// them back and emits no instruction.  What pays is the chest's limits: a scalar load the loop
+// issues on every update.  Read ahead of the integrates, and the chest's
+// maximum late in its stage, the load has ten vector instructions to arrive in where the joint-
+// by-joint order left it four.
+#ifdef __HIP_DEVICE_COMPILE__
+#define IKG_STAGE_FENCE() __builtin_amdgcn_sched_barrier(0)
+#else
+#define IKG_STAGE_FENCE() ((void)0)
+#endif
+template <typename T>
+IKG_HD inline void arm_update_staged(const KModel<typename LaneT<T>::E>* __restrict__ m, T dt, T s, const T* dq, T& qc, T* qa,
+                                     const ArmLimits<T>& lim) {
+  static_assert(is_f64<T>, "the staged clamp: the fp64 pair loop only");
+  const T root_lo = T(m->root_lo), root_hi = T(m->root_hi);
+  T v[7];
+  v[6] = qc + s * dt;  // first, as in arm_update: the step's operands are waited for once
+#pragma unroll
+  for (int k = 0; k < kArmDof; ++k) v[k] = qa[k] + dq[k] * dt;
+  IKG_STAGE_FENCE();
+#pragma unroll
+  for (int k = 0; k < kArmDof; ++k) v[k] = fmax(lim.lo[k], v[k]);
+  v[6] = fmax(root_lo, v[6]);
+  IKG_STAGE_FENCE();
+#pragma unroll
+  for (int k = 0; k < 3; ++k) qa[k] = fmin(v[k], lim.hi[k]);
+  qc = fmin(v[6], root_hi);  // mid-stage: clear of its maximum above and of the trig advance's first reader below
+#pragma unroll
+  for (int k = 3; k < kArmDof; ++k) qa[k] = fmin(v[k], lim.hi[k]);
+  IKG_STAGE_FENCE();
+}
+
 // tools.getcubeplacement: oMcube * hook (tools.py:54-59), for this lane's arm.
 template <typename T>
 IKG_HD inline void hook_target(const KModel<T>* __restrict__ m, int arm, const T* __restrict__ tg, T* RT,

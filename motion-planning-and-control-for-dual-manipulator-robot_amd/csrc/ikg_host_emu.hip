@@ -291,6 +291,41 @@ extern "C" void ikg_emu_force_general(int on) { force_general = on != 0; }
 // taken, or only where this problem's own angle asks for it (0); tests/test_log6_rare_path.py
 extern "C" void ikg_emu_force_small_angle(int on) { ikg_emu_small_angle = on != 0; }
 
+// The end of one update of the fp64 pair loop (integrate + clamp, trig advance) for n cases of one
+// arm each: staged = 0 runs arm_update (the `lim` path), staged != 0 the stage-by-stage form the
+// record-free kernel runs (arm_update_staged), either followed by trig_advance_f1<double, false,
+// true>; tests/test_seam_stage_order.py compares their bits.  in [n][22]: s, dq[6], qc, qa[6],
+// sn[7], resync flag; cs [n][7]; out [n][21]: qc, qa[6], sn[7], cs[7].
+extern "C" int ikg_emu_seam(const ikg_model_desc* d, int staged, int64_t n, const int32_t* arm, double dt,
+                            const double* in, const double* cs_in, double* out) {
+  using namespace ikg;
+  static thread_local KModel<double> m;
+  build_kmodel<double>(*d, m);
+  for (int64_t i = 0; i < n; ++i) {
+    const double* x = in + 22 * i;
+    const double s = x[0];
+    double dq[6], qc = x[7], qa[kArmDof], q_old[7], sn[7], cs[7];
+    for (int k = 0; k < 6; ++k) dq[k] = x[1 + k];
+    for (int k = 0; k < kArmDof; ++k) qa[k] = x[8 + k];
+    for (int j = 0; j < 7; ++j) sn[j] = x[14 + j], cs[j] = cs_in[7 * i + j];
+    const bool resync = x[21] != 0.0;
+    q_old[0] = qc;
+    for (int k = 0; k < kArmDof; ++k) q_old[k + 1] = qa[k];
+    ArmLimits<double> lim;
+    load_limits(&m, arm[i], lim);
+    if (staged)
+      arm_update_staged<double>(&m, dt, s, dq, qc, qa, lim);
+    else
+      arm_update(&m, arm[i], dt, s, dq, qc, qa, &lim);
+    trig_advance_f1<double, false, true>(&m, arm[i], qc, qa, q_old, resync, sn, cs);
+    double* o = out + 21 * i;
+    o[0] = qc;
+    for (int k = 0; k < kArmDof; ++k) o[1 + k] = qa[k];
+    for (int j = 0; j < 7; ++j) o[7 + j] = sn[j], o[14 + j] = cs[j];
+  }
+  return 0;
+}
+
 // The kernel's z-aligned test (z_aligned on hook_target's rotation) of n targets
 // [n][12]: out[2 i + arm] = 1 where arm's hook target of target i passes.
 template <typename T>

@@ -295,6 +295,9 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
   constexpr bool RETIRE = kScalarRetire<T, DAMPED, SP, REC>;
   constexpr bool COLD = RETIRE;
   static_assert(!ZT || RETIRE, "z-aligned targets: the record-free frame-1 pair loop only");
+  // the fp64 loop with the short trig rule integrates and clamps stage by stage across the joints
+  // (ikg_device.hpp arm_update_staged; same bits)
+  constexpr bool STAGED = RETIRE && is_f64<T> && !MED;
   uint64_t done = 0, live = 0;  // RETIRE: the lanes whose outputs are written / that entered the loop
   if constexpr (RETIRE) live = __builtin_amdgcn_ballot_w64(true);
   int stop_at = prm.max_iters;  // RETIRE: the count at which the loop leaves
@@ -497,7 +500,10 @@ __device__ inline bool solve_pair(const KModel<typename LaneT<T>::E>* __restrict
     IKG_STAMP(sc_t1);
     sc_acc[2] += sc_t1 - sc_t0;
 #endif
-    arm_update(m, arm, T(prm.dt), s, dq, qc, qa, limp);
+    if constexpr (STAGED)
+      arm_update_staged<T>(m, T(prm.dt), s, dq, qc, qa, lim);
+    else
+      arm_update(m, arm, T(prm.dt), s, dq, qc, qa, limp);
     if constexpr (REC == 1) {  // the window's path length: this update's largest joint step
       T mv = fabs(qc - q_old[0]);
 #pragma unroll
