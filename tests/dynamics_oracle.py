@@ -381,21 +381,29 @@ def seeded_inertias(nq, seed):
     return BodyInertias(mass, com, inertia).validate()
 
 
-def hanging_passive_model(model):
-    """`model` with its first passive joint re-parented below the second joint
-    of arm 0 and moved to the end of the q order (parents precede children):
-    a passive chain hanging below an arm joint.  Returns (DualArmModel, perm)
-    with new joint k = old joint perm[k]."""
+def hanging_passive_model(model, chain=None, below=None):
+    """`model` with a serial chain of passive joints (`chain`, head first;
+    default: the first passive joint alone) re-parented with its head below
+    joint `below` (default: the second joint of arm 0) and moved to the end of
+    the q order (parents precede children): a passive chain hanging below an
+    arm joint.  Returns (DualArmModel, perm) with new joint k = old joint perm[k]."""
     import copy
-    p = int(model.passive_q[0])
-    perm = [j for j in range(model.nq) if j != p] + [p]
+    chain = [int(model.passive_q[0])] if chain is None else [int(j) for j in chain]
+    below = int(model.arm_q[0][1]) if below is None else int(below)
+    passive = set(model.passive_q)
+    if not chain or len(set(chain)) != len(chain) or any(j not in passive for j in chain) or below in chain:
+        raise ValueError("the chain must be distinct passive joints, and hang below a joint outside it")
+    for a, b in zip(chain[:-1], chain[1:]):
+        if model.parents[b] != a:
+            raise ValueError("the chain must be serial, head first")
+    perm = [j for j in range(model.nq) if j not in chain] + chain
     new_of = {old: k for k, old in enumerate(perm)}
     m = copy.deepcopy(model)
     parents = list(model.parents)
-    parents[p] = int(model.arm_q[0][1])
+    parents[chain[0]] = below
     for old in range(model.nq):
-        if old != p and parents[old] == p:
-            raise ValueError("the passive joint must be a leaf")
+        if old not in chain and parents[old] in chain:
+            raise ValueError("the passive chain must end in a leaf")
     m.joint_names = [model.joint_names[o] for o in perm]
     m.parents = [new_of[parents[o]] if parents[o] >= 0 else -1 for o in perm]
     for name in ("R", "t", "axis", "lower", "upper"):

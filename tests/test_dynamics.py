@@ -3,7 +3,8 @@ inertia compile, the oracle (tests/dynamics_oracle.py) against the definitions
 of the quantities -- none of which shares code with the algorithms under test
 (Pinocchio is not importable here) -- the host emulation of the kernels'
 arithmetic against the fixtures (tests/golden/dynamics_cases.npz, whose tol_*
-entries are the measured bounds), and the C-ABI argument checks."""
+entries are the measured bounds), and the C-ABI argument checks.  The
+emulation on every robot-family tree: tests/test_dynamics_family.py."""
 import ctypes as C
 import os
 import subprocess

@@ -5,7 +5,10 @@ tests/golden/dynamics_cases.npz (make_dynamics_golden.py).
 Bounds: fp64 M / nle / g 1e-12 x max(1, max|fixture|); fp32 M / nle / g and
 the controller outputs: the measured bounds stored in the fixture (tol32_*:
 8 x the float32 oracle's error; tol_*: 20 x the float64 restatement's error
-against the 50-digit evaluation, relative to max|output|)."""
+against the 50-digit evaluation, relative to max|output|).
+
+The same kernels on every robot-family tree (nq = 13 ... 32, both lane groups,
+both branches of tile_store): tests/test_gpu_dynamics_family.py."""
 import os
 
 import numpy as np
