@@ -710,6 +710,73 @@ int ikg_trajectory_check_batch(const ikg_model* model, int device, const ikg_bez
                                const ikg_trajcheck_params* params, const ikg_trajcheck_out* out, void* stream,
                                uint32_t flags);
 
+/* ---- Trajectory dynamics: inverse dynamics and actuator limits along curves ----
+ * ikg_trajectory_dynamics_batch samples each of B joint-space Bezier curves at
+ * the S times of ikg_trajectory_check_batch and answers whether the motors can
+ * follow the curve in T = t_max - t_min, and if not how long it must take.
+ * fp64; M is never formed.  Per (curve b, sample k, joint j):
+ *   t_k = t_min + k T / (S - 1), t_{S-1} = t_max exactly
+ *   q   = the curve at t_k (ikg_bezier_eval_batch's function)
+ *   v   = the same function of the derivative points n (P[i+1] - P[i]), n the
+ *         degree, with multiplier mult * (1 / T); a = the same again from the v
+ *         points, multiplier mult * (1 / T) * (1 / T) (Bezier.derivative(1), (2);
+ *         every difference and product rounded, no fused multiply-add)
+ *   tau = rnea(q, v, a), g = rnea(q, 0, 0) (recursive Newton-Euler, the body
+ *         inertias and gravity of ikg_model_set_inertia), d = tau - g
+ * Under a uniform time scaling t -> s t the curve keeps its points, v scales as
+ * 1 / s and d as 1 / s^2, so the least feasible duration is a closed form of the
+ * samples.  Per curve, with velocity_limit vlim_j and effort_limit E_j:
+ *   speed_scale  = max |v| / vlim                     arg_speed
+ *   torque_use   = max |tau| / E at the curve's own T arg_torque_use
+ *   static_use   = max |g| / E                        arg_static
+ *   n_static     = entries with |g| >= E: no duration helps these
+ *   torque_scale = max over the other entries of sqrt(|d| / (E - sign(d) g)),
+ *                  0 where d = 0                      arg_torque_scale
+ * A duration s T meets every limit iff n_static == 0 and
+ * s >= max(speed_scale, torque_scale).  A joint whose limit is IKG_NO_LIMIT
+ * contributes 0.  Each arg output is [B,2] = (sample, joint) of the maximum;
+ * among exact ties the lowest sample, then the lowest joint; (-1, -1) and a
+ * value of 0 where no entry took part (torque_scale with every entry static).
+ * Per sample, on request: tau, g [B,S,nq].  Every output is optional (NULL).
+ *   q_curves->points [B, n_points, nq] and the outputs: device arrays, or host
+ *     arrays with IKG_FLAG_HOST_POINTERS; the limits travel in params
+ * A sample occupies 16 lanes (nq <= 16) or 32, one lane per body; one 64-lane
+ * wave walks samples_per_wave consecutive samples of one curve, 4 or 2 side by
+ * side, and a second kernel folds the waves' partial results per curve.  No
+ * output depends on samples_per_wave (0: whole lane groups, about 8,192 waves).
+ * n_points 5 .. 64 (below degree 4 the acceleration curve has two control
+ * points, which the reference's Bezier evaluates as a constant), S >= 2,
+ * t_max > t_min, every limit > 0.  A host-pointer call checks these and the
+ * finiteness of its inputs and returns IKG_EINVAL before any launch; the limits
+ * are checked with device pointers too.  Needs ikg_model_set_inertia.  B == 0 is
+ * a no-op.  Stream-ordered; the scratch comes from the model's pool.  Not
+ * capturable.
+ */
+#define IKG_NO_LIMIT 1e30
+typedef struct ikg_trajdyn_params {
+  int32_t samples;                   /* S >= 2; 151 */
+  int32_t samples_per_wave;          /* 0 = chosen by the launcher; >= 1 forces it (tests) */
+  double velocity_limit[IKG_MAX_NQ]; /* > 0; IKG_NO_LIMIT = unlimited */
+  double effort_limit[IKG_MAX_NQ];
+} ikg_trajdyn_params;
+typedef struct ikg_trajdyn_out { /* every field optional (NULL) */
+  void* speed_scale;             /* [B] */
+  int32_t* arg_speed;            /* [B,2] (sample, joint) */
+  void* torque_use;
+  int32_t* arg_torque_use;
+  void* static_use;
+  int32_t* arg_static;
+  int32_t* n_static; /* [B] */
+  void* torque_scale;
+  int32_t* arg_torque_scale;
+  void* tau; /* [B,S,nq] */
+  void* g;   /* [B,S,nq] */
+} ikg_trajdyn_out;
+void ikg_trajdyn_params_default(ikg_trajdyn_params* p); /* 151, 0, every limit IKG_NO_LIMIT */
+int ikg_trajectory_dynamics_batch(const ikg_model* model, int device, const ikg_bezier_set* q_curves, int64_t B,
+                                  const ikg_trajdyn_params* params, const ikg_trajdyn_out* out, void* stream,
+                                  uint32_t flags);
+
 /* Thread-local message of the last failure ("" if none). */
 const char* ikg_last_error(void);
 

@@ -1797,6 +1797,86 @@ int ikg_trajectory_check_batch(const ikg_model* model, int device, const ikg_bez
   return rc ? rc : st.finish(true);  // the staged pair list is freed on return
 }
 
+void ikg_trajdyn_params_default(ikg_trajdyn_params* p) {
+  if (!p) return;
+  p->samples = 151;  // the trajectory check's
+  p->samples_per_wave = 0;
+  for (int j = 0; j < IKG_MAX_NQ; ++j) p->velocity_limit[j] = p->effort_limit[j] = IKG_NO_LIMIT;
+}
+
+int ikg_trajectory_dynamics_batch(const ikg_model* model, int device, const ikg_bezier_set* q_curves, int64_t B,
+                                  const ikg_trajdyn_params* params, const ikg_trajdyn_out* out, void* stream,
+                                  uint32_t flags) {
+  g_err[0] = 0;
+  if (!model) return fail(IKG_EINVAL, "model is NULL");
+  if (!params) return fail(IKG_EINVAL, "params is NULL");
+  if (!out) return fail(IKG_EINVAL, "out is NULL");
+  if (B < 0) return fail(IKG_EINVAL, "B must be >= 0");
+  const int S = params->samples;
+  if (S < 2) return fail(IKG_EINVAL, "samples must be >= 2");
+  if (params->samples_per_wave < 0) return fail(IKG_EINVAL, "samples_per_wave must be >= 0");
+  if (!model->ine.present) return fail(IKG_EINVAL, "%s", model->ine.missing);
+  const int nq = model->desc.nq;
+  for (int j = 0; j < nq; ++j) {  // (!(x > 0) refuses a NaN; an infinite limit is written IKG_NO_LIMIT)
+    if (!(params->velocity_limit[j] > 0) || !std::isfinite(params->velocity_limit[j]))
+      return fail(IKG_EINVAL, "velocity_limit[%d] must be > 0 and finite (IKG_NO_LIMIT = unlimited)", j);
+    if (!(params->effort_limit[j] > 0) || !std::isfinite(params->effort_limit[j]))
+      return fail(IKG_EINVAL, "effort_limit[%d] must be > 0 and finite (IKG_NO_LIMIT = unlimited)", j);
+  }
+  if (q_curves && q_curves->n_points < ikg::kTrajDynMinPoints)
+    return fail(IKG_EINVAL, "q_curves: %d control points, the acceleration curve needs at least %d",
+                q_curves->n_points, ikg::kTrajDynMinPoints);
+  if (int rc = check_bezier_set(q_curves, nq, B, flags, "q_curves")) return rc;
+  const int spw = ikg::trajdyn_samples_per_wave(B > 0 ? B : 1, S, params->samples_per_wave, nq <= 16 ? 4 : 2);
+  const int chunks = (S + spw - 1) / spw;
+  if (B * chunks > kMaxWaves || B * (int64_t)S > (int64_t)1 << 40)
+    return fail(IKG_EINVAL, "B=%lld with %d samples is too large for one launch", (long long)B, S);
+  DeviceGuard g(device);
+  if (g.rc) return g.rc;
+  if (B == 0) return IKG_OK;
+  ikg_model* m = const_cast<ikg_model*>(model);
+  hipStream_t s = (hipStream_t)stream;
+  if (ikg::stream_capturing(s)) return fail(IKG_EINVAL, "ikg_trajectory_dynamics_batch is not capturable");
+  CtlTables t;
+  if (int rc = controller_tables(m, device, s, t)) return rc;
+  Staging st(s, flags);
+  ikg::TrajDynArgs a{};
+  a.points = (const double*)st.in(q_curves->points, sizeof(double) * q_curves->n_points * nq * B);
+  a.n_points = q_curves->n_points;
+  a.t_min = q_curves->t_min;
+  a.t_max = q_curves->t_max;
+  a.mult = q_curves->mult;
+  ikg::trajdyn_curve_setup(a);
+  a.S = S;
+  a.spw = spw;
+  a.chunks = chunks;
+  for (int j = 0; j < ikg::kMaxNq; ++j) {
+    a.vlim[j] = j < nq ? params->velocity_limit[j] : IKG_NO_LIMIT;
+    a.elim[j] = j < nq ? params->effort_limit[j] : IKG_NO_LIMIT;
+  }
+  const size_t rows = (size_t)B * S * nq;
+  a.tau = (double*)st.out(out->tau, sizeof(double) * rows);
+  a.g = (double*)st.out(out->g, sizeof(double) * rows);
+  ikg::TrajDynFoldOut o{};
+  o.speed_scale = (double*)st.out(out->speed_scale, sizeof(double) * B);
+  o.arg_speed = (int32_t*)st.out(out->arg_speed, sizeof(int32_t) * 2 * B);
+  o.torque_use = (double*)st.out(out->torque_use, sizeof(double) * B);
+  o.arg_torque_use = (int32_t*)st.out(out->arg_torque_use, sizeof(int32_t) * 2 * B);
+  o.static_use = (double*)st.out(out->static_use, sizeof(double) * B);
+  o.arg_static = (int32_t*)st.out(out->arg_static, sizeof(int32_t) * 2 * B);
+  o.n_static = (int32_t*)st.out(out->n_static, sizeof(int32_t) * B);
+  o.torque_scale = (double*)st.out(out->torque_scale, sizeof(double) * B);
+  o.arg_torque_scale = (int32_t*)st.out(out->arg_torque_scale, sizeof(int32_t) * 2 * B);
+  if (st.rc) return st.rc;
+  const int rc = with_scratch(m, sizeof(ikg::TrajDynPartial) * (size_t)B * chunks, s, "trajectory dynamics",
+                              [&](void* ws, const char*& what) {
+                                a.part = (ikg::TrajDynPartial*)ws;
+                                what = "ikg trajectory dynamics kernel launch";
+                                return ikg::launch_trajdyn(t.dm, t.di, nq, a, B, o, s);
+                              });
+  return rc ? rc : st.finish();
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------ model-specialised kernels

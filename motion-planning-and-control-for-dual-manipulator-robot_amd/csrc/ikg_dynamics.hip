@@ -24,7 +24,9 @@
 //
 // Further down: the controller solve (control.py:348-406), forward dynamics
 // qdd = M^-1 (tau - nle), the Bezier desired state (control.py:30-46) and the
-// per-tick step kernel of the closed-loop rollout (control.py:461-463).
+// per-tick step kernel of the closed-loop rollout (control.py:461-463), and
+// inverse dynamics with the actuator-limit ratios along Bezier curves
+// (ikg_trajectory_dynamics_batch).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,6 +34,7 @@
 
 #include "ikg_dynamics.hpp"
 #include "ikg_launch.hpp"
+#include "ikg_trajcheck.hpp"
 
 namespace ikg {
 
@@ -579,6 +582,170 @@ hipError_t launch_control_step(const CtlIn& in, int nq, int64_t B, const KCtl<do
     return a.cv.stride_q != 0 ? launch_step<G, true>(nblocks, in, nq, B, prm, a, s)
                               : launch_step<G, false>(nblocks, in, nq, B, prm, a, s);
   });
+}
+
+// ---------------------------------------------------------------- inverse dynamics along curves
+// ikg_trajectory_dynamics_batch: ikg_dynamics_kernel's layout (G lanes per
+// sample, one lane per body, parents by ds_bpermute) over the samples of a
+// curve.  One wave walks a.spw consecutive samples of one curve (block = curve *
+// a.chunks + chunk), 64 / G side by side; the groups of a ragged last round
+// repeat the run's last sample and store nothing.  The curve's control points
+// and those of its two derivatives (Bezier.derivative, formed here once per
+// wave) are staged in LDS; lane j does the Horner for joint j's q, qd, qdd, the
+// forward rounds with the acceleration included (dyn_forward_acc), both forces,
+// the subtree sums over j ascending, tau_j = S_j . fc and g_j = S_j . gc.  A lane
+// folds its own joint over the run, a butterfly folds the lanes (peak_merge does
+// not depend on the order), lane 0 writes the run's partial; the second kernel
+// folds the runs per curve.
+namespace {
+
+__device__ inline void peak_fold_lanes(DynPeak& p) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    DynPeak o;
+    o.val = __shfl_xor(p.val, off, 64);
+    o.sample = __shfl_xor(p.sample, off, 64);
+    o.joint = __shfl_xor(p.joint, off, 64);
+    peak_merge(p, o);
+  }
+}
+
+}  // namespace
+
+template <int G>
+__global__ __launch_bounds__(64) void ikg_trajdyn_kernel(const KModel<double>* __restrict__ m,
+                                                         const KInertia<double>* __restrict__ in,
+                                                         const TrajDynArgs a) {
+  using T = double;
+  extern __shared__ __align__(16) unsigned char smem[];
+  constexpr int kSide = 64 / G;
+  const int nq = m->nq, n = a.n_points;
+  T* Pq = reinterpret_cast<T*>(smem);
+  T* Pv = Pq + n * nq;
+  T* Pa = Pv + (n - 1) * nq;
+  const int lane = threadIdx.x;
+  const int grp = lane / G, b = lane % G, gbase = grp * G;
+  const int64_t curve = blockIdx.x / a.chunks;
+  const int ch = (int)(blockIdx.x % a.chunks);
+  const int k0 = ch * a.spw, k1 = min(a.S, k0 + a.spw);
+  const T* gp = a.points + curve * n * nq;
+  for (int i = lane; i < n * nq; i += 64) Pq[i] = gp[i];
+  __syncthreads();
+  for (int i = lane; i < (n - 1) * nq; i += 64) Pv[i] = bezier_derivative_point(Pq, n, nq, i / nq, i % nq);
+  __syncthreads();
+  for (int i = lane; i < (n - 2) * nq; i += 64) Pa[i] = bezier_derivative_point(Pv, n - 1, nq, i / nq, i % nq);
+  __syncthreads();
+  const KBezier<T> cq{Pq, a.bc[0], n, nq, a.t_min, a.t_max, a.mult};
+  const KBezier<T> cv{Pv, a.bc[1], n - 1, nq, a.t_min, a.t_max, a.mult_v};
+  const KBezier<T> ca{Pa, a.bc[2], n - 2, nq, a.t_min, a.t_max, a.mult_a};
+  // this lane's joint and body (idle lanes: a massless joint under the universe)
+  const bool body = b < nq;
+  const int bi = body ? b : 0;
+  T jR[9], jt[3], h[3], Io[6];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) jR[i] = m->jR[bi][i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) jt[i] = m->jt[bi][i];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) h[i] = body ? in->h[bi][i] : T(0);
+#pragma unroll
+  for (int i = 0; i < 6; ++i) Io[i] = body ? in->Io[bi][i] : T(0);
+  const T mass = body ? in->mass[bi] : T(0);
+  const int axis = m->jaxis[bi];
+  const int parent = body ? m->jparent[bi] : -1;
+  const T grav[3] = {in->grav[0], in->grav[1], in->grav[2]};
+  const T ref[3] = {in->ref[0], in->ref[1], in->ref[2]};
+  const int levels = in->levels;
+  const T vlim = a.vlim[bi], elim = a.elim[bi];
+  const int src = parent >= 0 ? gbase + parent : lane;
+  DynBody<T> uni;
+  dyn_universe(grav, ref, uni);
+  const T zero[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
+  TrajDynPartial part;
+  dynpartial_init(part);
+#pragma unroll 1
+  for (int kb = k0; kb < k1; kb += kSide) {
+    const bool on = kb + grp < k1;
+    const int k = on ? kb + grp : k1 - 1;
+    const T t = trajcheck_time(a.t_min, a.t_max, a.S, k);
+    const T q = body ? bezier_eval(cq, t, b) : T(0);
+    const T qd = body ? bezier_eval(cv, t, b) : T(0);
+    const T qdd = body ? bezier_eval(ca, t, b) : T(0);
+    T s, c;
+    cw_sincos(q, &s, &c);
+    DynBody<T> me = uni;
+    T S[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
+#pragma unroll 1
+    for (int l = 0; l < levels; ++l) {
+      DynBody<T> par;
+      lane_get_n(me.R, src, par.R);
+      lane_get_n(me.o, src, par.o);
+      lane_get_n(me.v, src, par.v);
+      lane_get_n(me.a, src, par.a);
+      if (parent < 0) par = uni;
+      dyn_forward_acc(par, jR, jt, axis, s, c, qd, qdd, me, S);
+    }
+    DynInertia<T> W;
+    dyn_inertia_world(mass, h, Io, me.R, me.o, W);
+    T f[6], f0[6];
+    dyn_force(W, me.v, me.a, f);
+    dyn_force(W, zero, uni.a, f0);
+    T fc[6] = {T(0), T(0), T(0), T(0), T(0), T(0)}, gc[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
+#pragma unroll 1
+    for (int j = 0; j < nq; ++j) {
+      const bool mine = (in->anc[j] >> b) & 1;  // j in the subtree of b
+      T fj[6], gj[6];
+      lane_get_n(f, gbase + j, fj);
+      lane_get_n(f0, gbase + j, gj);
+      if (mine) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+          fc[i] += fj[i];
+          gc[i] += gj[i];
+        }
+      }
+    }
+    const T tau = ddot6(S, fc), g = ddot6(S, gc);
+    if (on && body) {
+      dynpartial_add(part, k, b, qd, tau, g, vlim, elim);
+      const int64_t at = (curve * a.S + k) * nq + b;
+      if (a.tau) a.tau[at] = tau;
+      if (a.g) a.g[at] = g;
+    }
+  }
+  peak_fold_lanes(part.speed);
+  peak_fold_lanes(part.torque_use);
+  peak_fold_lanes(part.static_use);
+  peak_fold_lanes(part.torque_scale);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) part.n_static += __shfl_xor(part.n_static, off, 64);
+  if (lane == 0) a.part[blockIdx.x] = part;
+}
+
+// The runs' partials of each curve folded in sample order, one lane per curve.
+__global__ __launch_bounds__(256) void ikg_trajdyn_fold_kernel(const TrajDynPartial* __restrict__ part, int chunks,
+                                                               int64_t B, const TrajDynFoldOut o) {
+  const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  TrajDynPartial acc = part[b * chunks];
+  for (int ch = 1; ch < chunks; ++ch) dynpartial_merge(acc, part[b * chunks + ch]);
+  dynfold_store(o, b, acc);
+}
+
+hipError_t launch_trajdyn(const KModel<double>* dm, const KInertia<double>* di, int nq, const TrajDynArgs& a, int64_t B,
+                          const TrajDynFoldOut& o, hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  const size_t lds = sizeof(double) * (size_t)(3 * a.n_points - 3) * nq;
+  const unsigned nblocks = (unsigned)(B * a.chunks);
+  if (nq <= 16)
+    hipLaunchKernelGGL((ikg_trajdyn_kernel<16>), dim3(nblocks), dim3(64), lds, s, dm, di, a);
+  else
+    hipLaunchKernelGGL((ikg_trajdyn_kernel<32>), dim3(nblocks), dim3(64), lds, s, dm, di, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(ikg_trajdyn_fold_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, a.part, a.chunks, B,
+                     o);
+  return hipGetLastError();
 }
 
 template hipError_t launch_dynamics<double>(const KModel<double>*, const KInertia<double>*, int, const void*,

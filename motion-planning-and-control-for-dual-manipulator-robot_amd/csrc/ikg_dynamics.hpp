@@ -854,4 +854,224 @@ inline void control_step_state(int nq, const KCtl<T>& p, const T* M, const T* nl
   for (int r = 0; r < nq; ++r) step_integrate(dt, f.qdd[r], q[r], v[r]);
 }
 
+// ---------------------------------------------------------------- inverse dynamics along curves
+// ikg_trajectory_dynamics_batch: recursive Newton-Euler with the joint
+// acceleration included, tau = rnea(q, qd, qdd), beside g = rnea(q, 0, 0), at
+// the samples of a curve, and the actuator-limit ratios folded per curve.  M is
+// never formed.
+//
+// dyn_forward with the joint acceleration: a_i = a_p + S_i qdd_i + (v_i x S_i) qd_i.
+// A function of its own beside dyn_forward: the existing kernels keep theirs as
+// it is (sharing the forward pass moved their last bits, ikg_dynamics.hip).
+template <typename T>
+IKG_HD inline void dyn_forward_acc(const DynBody<T>& par, const T* jR, const T* jt, int axis, T s, T c, T qd, T qdd,
+                                   DynBody<T>& b, T* S) {
+  T P[9], d[3], ax[3];
+  matmul3(par.R, jR, P);
+  matvec3(par.R, jt, d);
+  const T e0 = T(axis == 0), e1 = T(axis == 1), e2 = T(axis == 2);
+  const T omc = T(1) - c;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const T r0 = P[3 * r], r1 = P[3 * r + 1], r2 = P[3 * r + 2];
+    const T u = e0 * r0 + e1 * r1 + e2 * r2;
+    ax[r] = u;
+    b.R[3 * r + 0] = c * r0 + s * (e2 * r1 - e1 * r2) + omc * u * e0;
+    b.R[3 * r + 1] = c * r1 + s * (e0 * r2 - e2 * r0) + omc * u * e1;
+    b.R[3 * r + 2] = c * r2 + s * (e1 * r0 - e0 * r1) + omc * u * e2;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) b.o[i] = par.o[i] + d[i];
+  dcross(b.o, ax, S);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) S[3 + i] = ax[i];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) b.v[i] = par.v[i] + S[i] * qd;
+  T t1[3], t2[3], t3[3];
+  dcross(b.v + 3, S, t1);
+  dcross(b.v, S + 3, t2);
+  dcross(b.v + 3, S + 3, t3);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    b.a[i] = par.a[i] + S[i] * qdd + (t1[i] + t2[i]) * qd;
+    b.a[3 + i] = par.a[3 + i] + S[3 + i] * qdd + t3[i] * qd;
+  }
+}
+
+// One state on the host in the trajectory-dynamics kernel's order: forward pass
+// with accelerations, both forces per body, subtree sums over j ascending.
+// tau [nq] = rnea(q, v, a), g [nq] = rnea(q, 0, 0).
+template <typename T>
+inline void inverse_dynamics_state(const KModel<T>& m, const KInertia<T>& in, const T* q, const T* v, const T* a,
+                                   T* tau, T* g) {
+  const int nq = m.nq;
+  DynBody<T> body[kMaxNq], uni;
+  T S[kMaxNq][6], f[kMaxNq][6], f0[kMaxNq][6];
+  dyn_universe(in.grav, in.ref, uni);
+  const T zero[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
+  for (int i = 0; i < nq; ++i) {
+    T s, c;
+    cw_sincos(q[i], &s, &c);
+    const DynBody<T>& par = m.jparent[i] >= 0 ? body[m.jparent[i]] : uni;
+    dyn_forward_acc(par, m.jR[i], m.jt[i], m.jaxis[i], s, c, v[i], a[i], body[i], S[i]);
+    DynInertia<T> W;
+    dyn_inertia_world(in.mass[i], in.h[i], in.Io[i], body[i].R, body[i].o, W);
+    dyn_force(W, body[i].v, body[i].a, f[i]);
+    dyn_force(W, zero, uni.a, f0[i]);
+  }
+  for (int i = 0; i < nq; ++i) {
+    T fc[6] = {T(0), T(0), T(0), T(0), T(0), T(0)}, gc[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
+    for (int j = 0; j < nq; ++j)
+      if ((in.anc[j] >> i) & 1)
+        for (int k = 0; k < 6; ++k) {
+          fc[k] += f[j][k];
+          gc[k] += f0[j][k];
+        }
+    tau[i] = ddot6(S[i], fc);
+    g[i] = ddot6(S[i], gc);
+  }
+}
+
+// Control point i, column col, of a curve's derivative (Bezier.derivative):
+// degree (P[i+1] - P[i]), the difference and the product each rounded
+template <typename T>
+IKG_HD inline T bezier_derivative_point(const T* P, int n_points, int dim, int i, int col) {
+#pragma clang fp contract(off)
+  const T d = P[(i + 1) * dim + col] - P[i * dim + col];
+  return T(n_points - 1) * d;
+}
+
+constexpr double kNoLimit = 1e30;   // IKG_NO_LIMIT
+constexpr int kTrajDynMinPoints = 5;  // below degree 4 the acceleration curve has two control points
+
+// A maximum with where it was found; among exact ties the lowest sample, then the lowest joint.
+// sample < 0: nothing folded yet.
+struct DynPeak {
+  double val;
+  int32_t sample, joint;
+};
+
+IKG_HD inline void peak_init(DynPeak& p) {
+  p.val = -1.0;
+  p.sample = p.joint = -1;
+}
+
+// order-independent: the larger value, then the lower (sample, joint)
+IKG_HD inline void peak_merge(DynPeak& a, const DynPeak& b) {
+  if (b.sample < 0) return;
+  const bool first = b.sample < a.sample || (b.sample == a.sample && b.joint < a.joint);
+  if (a.sample < 0 || b.val > a.val || (b.val == a.val && first)) a = b;
+}
+
+// A run of samples of one curve, folded: what a wave leaves in the scratch
+struct TrajDynPartial {
+  DynPeak speed, torque_use, static_use, torque_scale;
+  int32_t n_static, pad;
+};
+
+IKG_HD inline void dynpartial_init(TrajDynPartial& p) {
+  peak_init(p.speed);
+  peak_init(p.torque_use);
+  peak_init(p.static_use);
+  peak_init(p.torque_scale);
+  p.n_static = p.pad = 0;
+}
+
+IKG_HD inline void dynpartial_merge(TrajDynPartial& a, const TrajDynPartial& b) {
+  peak_merge(a.speed, b.speed);
+  peak_merge(a.torque_use, b.torque_use);
+  peak_merge(a.static_use, b.static_use);
+  peak_merge(a.torque_scale, b.torque_scale);
+  a.n_static += b.n_static;
+}
+
+// Entry (sample k, joint j) with velocity v, torques tau and g under the limits
+// vlim, E (kNoLimit: the joint contributes 0):
+//   speed |v| / vlim, torque use |tau| / E, static use |g| / E;
+//   |g| >= E: no duration helps, counted in n_static and left out of torque_scale;
+//   else with d = tau - g (scales as 1 / s^2 under t -> s t): the least s with
+//   |g + d / s^2| <= E is sqrt(|d| / (E - sign(d) g)), 0 where d = 0.
+IKG_HD inline void dynpartial_add(TrajDynPartial& p, int k, int j, double v, double tau, double g, double vlim,
+                                  double E) {
+  const bool vfree = vlim >= kNoLimit, efree = E >= kNoLimit;
+  const DynPeak sp{vfree ? 0.0 : fabs(v) / vlim, k, j};
+  const DynPeak tu{efree ? 0.0 : fabs(tau) / E, k, j};
+  const DynPeak su{efree ? 0.0 : fabs(g) / E, k, j};
+  peak_merge(p.speed, sp);
+  peak_merge(p.torque_use, tu);
+  peak_merge(p.static_use, su);
+  if (!efree && fabs(g) >= E) {
+    p.n_static += 1;
+    return;
+  }
+  const double d = tau - g;
+  double s = 0.0;
+  if (!efree && d != 0.0) s = sqrt(fabs(d) / (d > 0.0 ? E - g : E + g));
+  const DynPeak ts{s, k, j};
+  peak_merge(p.torque_scale, ts);
+}
+
+// Samples per wave where the caller leaves it open: runs of whole lane groups
+// (spg = 64 / G samples side by side) short enough for about kTrajDynWaves
+// waves, at most S.
+constexpr int64_t kTrajDynWaves = 8192;
+IKG_HD inline int trajdyn_samples_per_wave(int64_t B, int S, int forced, int spg) {
+  if (forced >= 1) return forced < S ? forced : S;
+  const int64_t want = (kTrajDynWaves + B - 1) / B;  // runs per curve
+  int64_t spw = (S + want - 1) / want;
+  spw = (spw + spg - 1) / spg * spg;
+  return (int)(spw < 1 ? 1 : (spw > S ? S : spw));
+}
+
+struct TrajDynArgs {
+  const double* points;  // [B, n_points, nq]
+  int n_points;
+  double t_min, t_max, mult, mult_v, mult_a;  // mult_v = mult (1 / T), mult_a = mult_v (1 / T)
+  int S, spw, chunks;
+  double *tau, *g;       // [B, S, nq], optional
+  TrajDynPartial* part;  // [B * chunks]
+  double bc[3][kMaxBezier];  // bezier_coeffs of the q, v and a curves
+  double vlim[kMaxNq], elim[kMaxNq];
+};
+
+// the curves' multipliers and binomial factors as Bezier.derivative forms them
+inline void trajdyn_curve_setup(TrajDynArgs& a) {
+  const double inv = 1.0 / (a.t_max - a.t_min);
+  a.mult_v = a.mult * inv;
+  a.mult_a = a.mult_v * inv;
+  std::memset(a.bc, 0, sizeof(a.bc));
+  for (int d = 0; d < 3; ++d) bezier_coeffs(a.n_points - d, a.bc[d]);
+}
+
+struct TrajDynFoldOut {
+  double* speed_scale;
+  int32_t* arg_speed;  // [B,2] (sample, joint)
+  double* torque_use;
+  int32_t* arg_torque_use;
+  double* static_use;
+  int32_t* arg_static;
+  int32_t* n_static;
+  double* torque_scale;
+  int32_t* arg_torque_scale;
+};
+
+IKG_HD inline void peak_store(double* val, int32_t* arg, int64_t b, const DynPeak& p) {
+  if (val) val[b] = p.sample < 0 ? 0.0 : p.val;
+  if (arg) {
+    arg[2 * b] = p.sample;
+    arg[2 * b + 1] = p.joint;
+  }
+}
+
+IKG_HD inline void dynfold_store(const TrajDynFoldOut& o, int64_t b, const TrajDynPartial& p) {
+  peak_store(o.speed_scale, o.arg_speed, b, p.speed);
+  peak_store(o.torque_use, o.arg_torque_use, b, p.torque_use);
+  peak_store(o.static_use, o.arg_static, b, p.static_use);
+  peak_store(o.torque_scale, o.arg_torque_scale, b, p.torque_scale);
+  if (o.n_static) o.n_static[b] = p.n_static;
+}
+
+hipError_t launch_trajdyn(const KModel<double>* dm, const KInertia<double>* di, int nq, const TrajDynArgs& a, int64_t B,
+                          const TrajDynFoldOut& o, hipStream_t s);
+
 }  // namespace ikg

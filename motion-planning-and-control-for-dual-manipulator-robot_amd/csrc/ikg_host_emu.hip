@@ -1137,3 +1137,65 @@ extern "C" int ikg_emu_trajectory_check(const ikg_model_desc* d, const ikg_colli
   }
   return 0;
 }
+
+// ---------------------------------------------------------------- trajectory dynamics on the CPU
+// ikg_trajectory_dynamics_batch with host pointers: the derivative control
+// points and multipliers as the launcher and the kernel form them, bezier_eval
+// per joint, inverse_dynamics_state, then dynpartial_add over the samples in
+// order, joints ascending (what the waves' partials fold to whatever the
+// chunking).  -1 where the entry returns IKG_EINVAL.  tests/test_trajdyn.py.
+extern "C" int ikg_emu_trajectory_dynamics(const ikg_model_desc* d, const ikg_inertia_desc* id,
+                                           const ikg_bezier_set* curves, int64_t B, const ikg_trajdyn_params* p,
+                                           const ikg_trajdyn_out* out) {
+  using namespace ikg;
+  if (!d || !id || !curves || !p || !out || B < 0) return -1;
+  if (B > 0 && !curves->points) return -1;
+  if (curves->n_points < kTrajDynMinPoints || curves->n_points > kMaxBezier || !(curves->t_max > curves->t_min))
+    return -1;
+  if (p->samples < 2 || p->samples_per_wave < 0) return -1;
+  const int nq = d->nq, S = p->samples, n = curves->n_points;
+  for (int j = 0; j < nq; ++j)
+    if (!(p->velocity_limit[j] > 0) || !(p->effort_limit[j] > 0) || !std::isfinite(p->velocity_limit[j]) ||
+        !std::isfinite(p->effort_limit[j]))
+      return -1;
+  const EmuTables<double>* t = emu_tables<double>(d, id);
+  if (!t) return -1;
+  static thread_local TrajDynArgs a;
+  a.n_points = n;
+  a.t_min = curves->t_min;
+  a.t_max = curves->t_max;
+  a.mult = curves->mult;
+  trajdyn_curve_setup(a);
+  const TrajDynFoldOut o{(double*)out->speed_scale, out->arg_speed,  (double*)out->torque_use,
+                         out->arg_torque_use,       (double*)out->static_use, out->arg_static,
+                         out->n_static,             (double*)out->torque_scale, out->arg_torque_scale};
+  std::vector<double> Pv((size_t)(n - 1) * nq), Pa((size_t)(n - 2) * nq);
+  for (int64_t b = 0; b < B; ++b) {
+    const double* Pq = (const double*)curves->points + b * n * nq;
+    for (int i = 0; i < (n - 1) * nq; ++i) Pv[i] = bezier_derivative_point(Pq, n, nq, i / nq, i % nq);
+    for (int i = 0; i < (n - 2) * nq; ++i) Pa[i] = bezier_derivative_point(Pv.data(), n - 1, nq, i / nq, i % nq);
+    const KBezier<double> cq{Pq, a.bc[0], n, nq, a.t_min, a.t_max, a.mult};
+    const KBezier<double> cv{Pv.data(), a.bc[1], n - 1, nq, a.t_min, a.t_max, a.mult_v};
+    const KBezier<double> ca{Pa.data(), a.bc[2], n - 2, nq, a.t_min, a.t_max, a.mult_a};
+    TrajDynPartial part;
+    dynpartial_init(part);
+    for (int k = 0; k < S; ++k) {
+      const double tk = trajcheck_time(a.t_min, a.t_max, S, k);
+      double q[kMaxNq], v[kMaxNq], acc[kMaxNq], tau[kMaxNq], g[kMaxNq];
+      for (int j = 0; j < nq; ++j) {
+        q[j] = bezier_eval(cq, tk, j);
+        v[j] = bezier_eval(cv, tk, j);
+        acc[j] = bezier_eval(ca, tk, j);
+      }
+      inverse_dynamics_state<double>(t->m, t->in, q, v, acc, tau, g);
+      for (int j = 0; j < nq; ++j) {
+        dynpartial_add(part, k, j, v[j], tau[j], g[j], p->velocity_limit[j], p->effort_limit[j]);
+        const int64_t at = (b * S + k) * nq + j;
+        if (out->tau) ((double*)out->tau)[at] = tau[j];
+        if (out->g) ((double*)out->g)[at] = g[j];
+      }
+    }
+    dynfold_store(o, b, part);
+  }
+  return 0;
+}

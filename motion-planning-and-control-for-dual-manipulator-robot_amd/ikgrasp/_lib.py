@@ -156,6 +156,28 @@ class TrajCheckOut(C.Structure):
     _fields_ = [(f[0], C.c_void_p) for f in TRAJCHECK_CURVE + TRAJCHECK_SAMPLE]
 
 
+NO_LIMIT = 1e30  # IKG_NO_LIMIT
+
+
+class TrajDynParams(C.Structure):
+    """ikg_trajdyn_params: samples per curve, samples per wave (0 = the launcher's choice), the joints'
+    velocity and effort limits (NO_LIMIT = unlimited)."""
+    _fields_ = [("samples", C.c_int32), ("samples_per_wave", C.c_int32),
+                ("velocity_limit", C.c_double * IKG_MAX_NQ), ("effort_limit", C.c_double * IKG_MAX_NQ)]
+
+
+# per curve: (name, dtype, trailing shape); an arg output holds (sample, joint)
+TRAJDYN_CURVE = (("speed_scale", np.float64, ()), ("arg_speed", np.int32, (2,)), ("torque_use", np.float64, ()),
+                 ("arg_torque_use", np.int32, (2,)), ("static_use", np.float64, ()), ("arg_static", np.int32, (2,)),
+                 ("n_static", np.int32, ()), ("torque_scale", np.float64, ()), ("arg_torque_scale", np.int32, (2,)))
+TRAJDYN_SAMPLE = ("tau", "g")  # [B,S,nq] float64
+
+
+class TrajDynOut(C.Structure):
+    """ikg_trajdyn_out: optional output pointers, per curve then per sample."""
+    _fields_ = [(f[0], C.c_void_p) for f in TRAJDYN_CURVE] + [(name, C.c_void_p) for name in TRAJDYN_SAMPLE]
+
+
 EXPORTS = [
     "ikg_model_create", "ikg_model_destroy", "ikg_params_default", "ikg_solve_batch",
     "ikg_solve_multistart", "ikg_fk_batch", "ikg_log6_batch", "ikg_last_error", "ikg_version",
@@ -166,6 +188,7 @@ EXPORTS = [
     "ikg_control_rollout_curves", "ikg_fit_params_default", "ikg_bezier_fit_batch",
     "ikg_se3_interpolate_batch", "ikg_nearest_batch", "ikg_project_paths",
     "ikg_trajcheck_params_default", "ikg_trajectory_check_batch", "ikg_trajcheck_samples_per_wave",
+    "ikg_trajdyn_params_default", "ikg_trajectory_dynamics_batch",
 ]
 
 _lib = None
@@ -270,6 +293,11 @@ def load() -> C.CDLL:
     lib.ikg_trajectory_check_batch.restype = i32
     lib.ikg_trajcheck_samples_per_wave.argtypes = [i64, C.c_int32]
     lib.ikg_trajcheck_samples_per_wave.restype = i32
+    lib.ikg_trajdyn_params_default.argtypes = [C.POINTER(TrajDynParams)]
+    lib.ikg_trajdyn_params_default.restype = None
+    lib.ikg_trajectory_dynamics_batch.argtypes = [vp, i32, C.POINTER(BezierSet), i64, C.POINTER(TrajDynParams),
+                                                  C.POINTER(TrajDynOut), vp, C.c_uint32]
+    lib.ikg_trajectory_dynamics_batch.restype = i32
     lib.ikg_model_specialize.argtypes = [vp, i32, i32, C.c_uint32]
     lib.ikg_model_specialize.restype = i32
     lib.ikg_model_is_specialized.argtypes = [vp, i32, i32]
@@ -400,6 +428,25 @@ def trajcheck_params(samples=151, cube_mode=CUBE_CARRIED, samples_per_wave=0) ->
     p = TrajCheckParams()
     load().ikg_trajcheck_params_default(C.byref(p))
     p.samples, p.cube_mode, p.samples_per_wave = int(samples), int(cube_mode), int(samples_per_wave)
+    return p
+
+
+def trajdyn_limits(limit, nq, what):
+    """None (unlimited), one number or [nq] numbers -> [nq] float64; inf and values above NO_LIMIT become NO_LIMIT"""
+    if limit is None:
+        return np.full(nq, NO_LIMIT)
+    v = np.broadcast_to(np.asarray(limit, dtype=np.float64), (nq,)).copy()
+    if np.isnan(v).any():
+        raise ValueError(f"{what} limits must be numbers")
+    return np.minimum(v, NO_LIMIT)
+
+
+def trajdyn_params(nq, samples=151, velocity=None, effort=None, samples_per_wave=0) -> TrajDynParams:
+    p = TrajDynParams()
+    load().ikg_trajdyn_params_default(C.byref(p))
+    p.samples, p.samples_per_wave = int(samples), int(samples_per_wave)
+    p.velocity_limit[:nq] = trajdyn_limits(velocity, nq, "velocity").tolist()
+    p.effort_limit[:nq] = trajdyn_limits(effort, nq, "effort").tolist()
     return p
 
 

@@ -25,7 +25,10 @@ function.  `maketraj` is the drop-in for the reference's trajectory fit
 (control.py:63-197) and `maketraj_batch` fits B paths in one launch of
 `ikg_bezier_fit_batch`; `save_trajectory` writes the reference's file.  `checktraj`
 samples fitted curves for collision, clearance, grasp error and joint limits
-in one launch of `ikg_trajectory_check_batch`.  `rollout` runs B closed loops of that law against a free-space
+in one launch of `ikg_trajectory_check_batch`; `dyntraj` answers whether the
+motors can follow them (inverse dynamics and the URDF's velocity and effort
+limits along the curve, `ikg_trajectory_dynamics_batch`) and `retime` stretches
+them to the least duration that meets every limit.  `rollout` runs B closed loops of that law against a free-space
 rigid-body plant in one call of `ikg_control_rollout` (desired state from the
 Bezier curves, torque law, forward dynamics, semi-implicit Euler), and
 `Simulation` is the same plant one tick at a time behind the simulator's
@@ -202,6 +205,10 @@ class FittedTrajectories:
         """`checktraj(robot, self, **kw)`: one verdict per fitted curve."""
         return checktraj(robot, self, **kw)
 
+    def dynamics(self, robot, **kw):
+        """`dyntraj(robot, self, **kw)`: the actuator-limit report of every fitted curve."""
+        return dyntraj(robot, self, **kw)
+
 
 def maketraj_batch(q0s, q1s, paths, total_time, degree=20, ridge=None, solver=None):
     """The reference's maketraj (control.py:63-197) for B paths in one launch of
@@ -283,6 +290,69 @@ def checktraj(robot, trajs, samples=151, cube="carried", min_clearance=0.0, max_
                                        per_sample=per_sample, **kw)
     report["ok"] = trajectory_ok(report, min_clearance, max_grasp)
     return report
+
+
+def _curve_set(trajs):
+    """trajs as `checktraj` takes them -> (points [B,n,nq], t_min, t_max, mult)"""
+    if isinstance(trajs, FittedTrajectories):
+        return np.asarray(trajs.points, dtype=np.float64), trajs.t_min, trajs.t_max, 1.0
+    q_of_t = trajs if hasattr(trajs, "control_points_") else trajs[0]
+    pts, t_min, t_max, mult = _lib.curve(q_of_t)
+    return pts[None], t_min, t_max, mult
+
+
+def dyntraj(robot, trajs, samples=151, velocity=None, effort=None, per_sample=False, **kw):
+    """Can the motors follow these curves in their duration, and if not how
+    long must they take?  Each curve is sampled at `samples` times (the times
+    of `checktraj`) in one launch of `ikg_trajectory_dynamics_batch` (GPU,
+    fp64): joint velocity and acceleration from the curve's derivatives, the
+    joint torques by recursive Newton-Euler, and their ratios to the limits.
+    trajs: as `checktraj`.  velocity, effort: the joints' limits; None = the
+    robot's (`robot.actuation`, the URDF's <limit velocity effort>), unlimited
+    for a robot without them.  -> the report of `IKSolver.curve_dynamics` plus
+    ok [B] = n_static == 0 and speed_scale <= 1 and torque_use <= 1, and
+    least_duration [B] = (t_max - t_min) max(speed_scale, torque_scale), the
+    shortest duration of the same curve that meets every limit (inf where
+    n_static > 0: a joint cannot hold the posture at any speed).  `kw`:
+    samples_per_wave."""
+    points, t_min, t_max, mult = _curve_set(trajs)
+    act = getattr(robot, "actuation", None)
+    if velocity is None and act is not None:
+        velocity = act.velocity
+    if effort is None and act is not None:
+        effort = act.effort
+    report = robot.solver.curve_dynamics(points, t_min, t_max, mult=mult, samples=samples, velocity=velocity,
+                                         effort=effort, per_sample=per_sample, **kw)
+    static = np.asarray(report["n_static"]) > 0
+    report["ok"] = ~static & (np.asarray(report["speed_scale"]) <= 1.0) & (np.asarray(report["torque_use"]) <= 1.0)
+    scale = np.maximum(np.asarray(report["speed_scale"]), np.asarray(report["torque_scale"]))
+    report["least_duration"] = np.where(static, np.inf, (float(t_max) - float(t_min)) * scale)
+    return report
+
+
+def retime(robot, trajs, margin=1.0, **kw):
+    """The same curve(s) at the least duration that meets every actuator limit
+    (`dyntraj`'s least_duration) times `margin`: uniform time scaling moves
+    t_max only, so nothing is fitted again.  One trajectory (a tuple as
+    `maketraj` returns, or a `Curve`) -> [q_of_t, vq_of_t, vvq_of_t] with
+    t_max = t_min + margin least_duration and the derivative curves rebuilt
+    from the new range.  A `FittedTrajectories` -> (durations [B] = margin
+    least_duration, a `FittedTrajectories` of the same control points whose
+    total_time is the largest of them: the shortest common duration at which
+    every curve is feasible).  ValueError where n_static > 0.  `kw`: dyntraj's."""
+    report = dyntraj(robot, trajs, **kw)
+    if (np.asarray(report["n_static"]) > 0).any():
+        bad = np.flatnonzero(np.asarray(report["n_static"]) > 0).tolist()
+        raise ValueError(f"curves {bad}: gravity alone exceeds an effort limit (n_static > 0), no duration is feasible")
+    durations = float(margin) * np.asarray(report["least_duration"], dtype=np.float64)
+    if not (durations > 0).all():
+        raise ValueError("a curve that does not move has no least duration")
+    if isinstance(trajs, FittedTrajectories):
+        return durations, FittedTrajectories(trajs.points, trajs.vpoints, trajs.apoints, trajs.cost,
+                                             float(durations.max()))
+    q_of_t = trajs if hasattr(trajs, "control_points_") else trajs[0]
+    q_new = Curve(q_of_t.control_points_, q_of_t.T_min_, q_of_t.T_min_ + float(durations[0]), q_of_t.mult_T_)
+    return [q_new, q_new.derivative(1), q_new.derivative(2)]
 
 
 def rollout(robot, q0, vq0, trajs, t0=None, ticks=1500, **kw):

@@ -94,6 +94,8 @@ class Joint:
     upper: float
     axis_dir: np.ndarray = None  # the URDF axis, normalised
     Q: np.ndarray = None         # joint-frame change with Q e_axis = axis_dir (I when aligned)
+    velocity: float = 0.0        # <limit velocity>, rad/s; 0 = not stated
+    effort: float = 0.0          # <limit effort>, N m; 0 = not stated
 
 
 def _unit(k: int) -> np.ndarray:
@@ -206,7 +208,9 @@ def parse_urdf(path_or_xml: str, base_placement=None) -> KinematicTree:
                 R, t = origin
                 if parent_joint < 0 and base_placement is not None:
                     R, t = _compose(base_placement, (R, t))
-                tree.joints.append(Joint(jname, parent_joint, R, t, code, lower, upper, e, Q))
+                velocity = float(lim.get("velocity", "0")) if lim is not None else 0.0
+                effort = float(lim.get("effort", "0")) if lim is not None else 0.0
+                tree.joints.append(Joint(jname, parent_joint, R, t, code, lower, upper, e, Q, velocity, effort))
                 idx = len(tree.joints) - 1
                 tree.frames[jname] = Frame(jname, idx, np.eye(3), np.zeros(3))
                 tree.frames[child] = Frame(child, idx, np.eye(3), np.zeros(3))
@@ -433,11 +437,57 @@ class BodyInertias:
                             np.array(d["inertia"], dtype=np.float64).reshape(-1, 6)).validate()
 
 
+@dataclass
+class ActuatorLimits:
+    """Per joint (q order) what the motor can do, from the URDF's
+    `<limit velocity= effort=>`: the largest joint speed (rad/s) and torque
+    (N m).  A missing or zero value is unlimited (np.inf).  Consumed by
+    `IKSolver.curve_dynamics` / `control.dyntraj` (ikg_trajdyn_params)."""
+    velocity: np.ndarray  # [nq]
+    effort: np.ndarray    # [nq]
+
+    @property
+    def nq(self) -> int:
+        return len(self.velocity)
+
+    @staticmethod
+    def from_tree(tree: KinematicTree) -> "ActuatorLimits":
+        lim = lambda x: float(x) if x > 0.0 else np.inf
+        return ActuatorLimits(np.array([lim(j.velocity) for j in tree.joints], dtype=np.float64),
+                              np.array([lim(j.effort) for j in tree.joints], dtype=np.float64)).validate()
+
+    @staticmethod
+    def from_urdf(robot_urdf: str) -> "ActuatorLimits":
+        return ActuatorLimits.from_tree(parse_urdf(robot_urdf))
+
+    def validate(self):
+        """every limit > 0 (np.inf = unlimited), one per joint"""
+        v, e = np.asarray(self.velocity, dtype=np.float64), np.asarray(self.effort, dtype=np.float64)
+        if v.ndim != 1 or v.shape != e.shape:
+            raise ValueError("ActuatorLimits: velocity and effort must be [nq]")
+        if not (np.all(v > 0) and np.all(e > 0)):  # refuses NaN too
+            raise ValueError("ActuatorLimits: every limit must be > 0 (np.inf = unlimited)")
+        self.velocity, self.effort = v, e
+        return self
+
+    def to_json(self) -> str:
+        """unlimited entries are written as null"""
+        row = lambda x: [None if np.isinf(t) else float(t) for t in x]
+        return json.dumps({"velocity": row(self.velocity), "effort": row(self.effort)}, indent=1)
+
+    @staticmethod
+    def from_json(text: str) -> "ActuatorLimits":
+        d = json.loads(text)
+        row = lambda x: np.array([np.inf if t is None else float(t) for t in x], dtype=np.float64)
+        return ActuatorLimits(row(d["velocity"]), row(d["effort"])).validate()
+
+
 GRAVITY = (0.0, 0.0, -9.81)  # Pinocchio's model.gravity and the simulator's (setup_pybullet.py:33), world frame
 
 DATA_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
 NEXTAGE_INERTIA_JSON = os.path.join(DATA_DIR, "nextage_inertia.json")
 NEXTAGE_JSON = os.path.join(DATA_DIR, "nextage_dualarm.json")
+NEXTAGE_ACTUATION_JSON = os.path.join(DATA_DIR, "nextage_actuation.json")
 
 
 def load_nextage() -> DualArmModel:
@@ -452,3 +502,10 @@ def load_nextage_inertia() -> BodyInertias:
     reference URDF's <inertial> entries)."""
     with open(NEXTAGE_INERTIA_JSON) as f:
         return BodyInertias.from_json(f.read())
+
+
+def load_nextage_actuation() -> ActuatorLimits:
+    """The Nextage joints' velocity and effort limits (compiled by
+    `tools/compile_model.py` from the reference URDF's <limit> entries)."""
+    with open(NEXTAGE_ACTUATION_JSON) as f:
+        return ActuatorLimits.from_json(f.read())

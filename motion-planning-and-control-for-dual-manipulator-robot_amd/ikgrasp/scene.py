@@ -42,6 +42,10 @@ class Robot:
             from .collision import load_nextage_scene
             scene = load_nextage_scene()
         self.scene = scene
+        self.actuation = None  # ActuatorLimits: what control.dyntraj / retime check a curve against
+        if self._default_model:  # the shipped Nextage tables come with the URDF's <limit velocity effort>
+            from .model import load_nextage_actuation
+            self.actuation = load_nextage_actuation()
         self._solver = None
 
     @property

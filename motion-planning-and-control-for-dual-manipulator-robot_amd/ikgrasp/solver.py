@@ -445,6 +445,44 @@ class IKSolver:
                                                        C.byref(out), s, flags))
         return res
 
+    # ------------------------------------------------------------------ trajectory dynamics (fp64)
+    def curve_dynamics(self, points, t_min, t_max, mult=1.0, samples=151, velocity=None, effort=None,
+                       per_sample=False, samples_per_wave=0, stream=None) -> dict:
+        """ikg_trajectory_dynamics_batch: inverse dynamics at `samples` times
+        along B joint-space Bezier curves and the actuator-limit ratios folded
+        per curve.  points [B, n_points, nq] (numpy, or a float64 ROCm tensor),
+        n_points 5 .. 64; velocity, effort: the joints' limits ([nq], one
+        number, or None / np.inf = unlimited).  -> dict of speed_scale,
+        torque_use, static_use, torque_scale [B], n_static [B] and arg_speed,
+        arg_torque_use, arg_static, arg_torque_scale [B,2] = (sample, joint);
+        with per_sample also tau, g [B,S,nq].  A duration s (t_max - t_min)
+        meets every limit iff n_static == 0 and s >= max(speed_scale,
+        torque_scale).  Needs `set_inertia`."""
+        if not _is_torch(points):
+            points = np.asarray(points, dtype=np.float64)
+        if points.ndim != 3 or points.shape[2] != self.nq:
+            raise ValueError(f"points must be [B, n_points, {self.nq}], got {list(points.shape)}")
+        B, n_points = int(points.shape[0]), int(points.shape[1])
+        S = int(samples)
+        prm = _lib.trajdyn_params(self.nq, S, velocity, effort, samples_per_wave)
+        prep, empty, ptr, s, device, flags = self._f64_io(points, stream)
+        flat = prep(points, n_points * self.nq)
+        if _is_torch(points):
+            import torch
+            kinds = {np.int32: torch.int32, np.float64: torch.float64}
+            alloc = lambda t, *shape: torch.empty(shape, dtype=kinds[t], device=points.device)
+        else:
+            alloc = lambda t, *shape: np.empty(shape, dtype=t)
+        res = {name: alloc(t, B, *tail) for name, t, tail in _lib.TRAJDYN_CURVE}
+        if per_sample:
+            res.update({name: alloc(np.float64, B, S, self.nq) for name in _lib.TRAJDYN_SAMPLE})
+        bset = _lib.BezierSet(ptr(flat), n_points, float(t_min), float(t_max), float(mult))
+        out = _lib.TrajDynOut(*[ptr(res.get(f[0])) for f in _lib.TRAJDYN_CURVE],
+                              *[ptr(res.get(name)) for name in _lib.TRAJDYN_SAMPLE])
+        _lib.check(self.lib.ikg_trajectory_dynamics_batch(self._h, device, C.byref(bset), B, C.byref(prm),
+                                                          C.byref(out), s, flags))
+        return res
+
     # ------------------------------------------------------------------ log6
     def log6(self, M, dtype="f64") -> np.ndarray:
         """pin.log6 of placements [B,12] -> [B,6] ([v; w])."""

@@ -2,10 +2,10 @@
 
     python tools/compile_model.py [/root/reference]
 
-Writes `<pkg>/ikgrasp/data/nextage_dualarm.json`, `nextage_inertia.json` and
-`nextage_collision.json` (committed: the GPU box has no reference tree).
-Inputs: `models/nextagea_description/urdf/NextageaOpen.urdf` (kinematics and
-the links' <inertial> entries) and `models/cubes/cube_small.urdf`
+Writes `<pkg>/ikgrasp/data/nextage_dualarm.json`, `nextage_inertia.json`,
+`nextage_actuation.json` and `nextage_collision.json` (committed: the GPU box has no reference tree).
+Inputs: `models/nextagea_description/urdf/NextageaOpen.urdf` (kinematics, the
+links' <inertial> entries and the joints' <limit velocity effort>) and `models/cubes/cube_small.urdf`
 (config.py:44-51), base placement
 ROBOT_PLACEMENT = (I, [0, 0, 0.85]) (config.py:33).
 """
@@ -18,7 +18,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", "motion-planning-and-control-for-dual-manipulator-robot_amd"))
 
 from ikgrasp.collision import NEXTAGE_COLLISION_JSON, build_scene  # noqa: E402
-from ikgrasp.model import BodyInertias, DualArmModel, NEXTAGE_INERTIA_JSON, NEXTAGE_JSON  # noqa: E402
+from ikgrasp.model import (ActuatorLimits, BodyInertias, DualArmModel, NEXTAGE_ACTUATION_JSON,  # noqa: E402
+                           NEXTAGE_INERTIA_JSON, NEXTAGE_JSON)
 from ikgrasp.se3 import rotate  # noqa: E402
 
 
@@ -36,6 +37,11 @@ def main(ref="/root/reference"):
     with open(NEXTAGE_INERTIA_JSON, "w") as f:
         f.write(bi.to_json())
     print(f"wrote {NEXTAGE_INERTIA_JSON}: {bi.nq} bodies, {bi.mass.sum():.6g} kg")
+    # what the motors can do (<limit velocity effort>): control.dyntraj / retime
+    al = ActuatorLimits.from_urdf(robot)
+    with open(NEXTAGE_ACTUATION_JSON, "w") as f:
+        f.write(al.to_json())
+    print(f"wrote {NEXTAGE_ACTUATION_JSON}: velocity {sorted(set(al.velocity.tolist()))} effort {sorted(set(al.effort.tolist()))}")
     # collision scene (setup_pinocchio.py:53-83; placements config.py:33-37)
     urdf = os.path.join(ref, "models/nextagea_description/urdf")
     scene = build_scene(
