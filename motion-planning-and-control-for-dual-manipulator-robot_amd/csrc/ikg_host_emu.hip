@@ -2,9 +2,11 @@
 // never called by libikgrasp.so): runs the exact stage functions of
 // ikg_device.hpp for both arm lanes of a problem on the CPU, in the order the
 // kernel's lanes execute them, so kernel numerics can be inspected without a
-// GPU.  Built as libikgrasp_emu.so; used by tests/test_host_emu.py.  Further
-// down: the collision, dynamics, controller and closed-loop rollout arithmetic
-// on the same terms (tests/test_collision.py, test_dynamics.py, test_rollout.py).
+// GPU.  Built as libikgrasp_emu.so.  Further down: the collision, dynamics,
+// controller and closed-loop rollout arithmetic on the same terms.
+// The library has no header: tests/emu.py's PROTOTYPES is its one declaration,
+// used by every test and tool, and tests/test_emu_binding.py compares that table
+// with the definitions in this file.  A new `extern "C"` export needs a row there.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>

@@ -13,6 +13,7 @@ import os
 
 import numpy as np
 
+import emu as host_emu
 import fit_oracle as fo
 from ikgrasp import _lib
 
@@ -54,8 +55,8 @@ def pack(paths):
 class EmuFit:
     """ikg_emu_bezier_fit (libikgrasp_emu.so) behind ikgrasp.solver.bezier_fit's signature, numpy only."""
 
-    def __init__(self, emu):
-        self.emu = emu
+    def __init__(self):
+        self.emu = host_emu.load()
 
     def bezier_fit(self, q0, q1, path_points, offsets, total_time=1.0, degree=20, ridge=0.0, derivatives=True):
         q0 = np.ascontiguousarray(q0, dtype=np.float64)
@@ -68,9 +69,9 @@ class EmuFit:
         res = {"points": np.full((B, d + 1, dim), -7.0), "cost": np.empty(B), "status": np.empty(B, dtype=np.int32)}
         if derivatives:
             res["vpoints"], res["apoints"] = np.empty((B, d, dim)), np.empty((B, d - 1, dim))
-        p = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+        p = lambda a: None if a is None else a.ctypes.data
         prm = _lib.FitParams(d, float(ridge), float(total_time))
-        rc = self.emu.ikg_emu_bezier_fit(p(q0), p(q1), p(y), p(off), C.c_int64(B), C.c_int32(dim), C.byref(prm),
+        rc = self.emu.ikg_emu_bezier_fit(p(q0), p(q1), p(y), p(off), B, dim, C.byref(prm),
                                          p(res["points"]), p(res.get("vpoints")), p(res.get("apoints")),
                                          p(res["cost"]), p(res["status"]))
         if rc:
@@ -189,10 +190,9 @@ def per_state_rollout(solver, q0, v0, sets, t0=None, ticks=0, dt_sim=1e-3, dt_tr
     res = {k: np.empty(shape(k)) for k in outputs}
     out = _lib.RolloutOut(*[None if k not in res else res[k].ctypes.data
                             for k in ("q", "v", "t", "q_hist", "v_hist", "tau_hist")])
-    p = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
-    rc = solver.emu.ikg_emu_control_rollout_curves(C.byref(solver.desc), C.byref(solver.idesc), p(q0), p(v0), p(t0),
-                                                   C.c_int64(B), C.byref(bs[0]), C.byref(bs[1]), C.byref(prm),
-                                                   C.byref(out))
+    p = lambda a: None if a is None else a.ctypes.data
+    rc = solver.emu.ikg_emu_control_rollout_curves(C.byref(solver.desc), C.byref(solver.idesc), p(q0), p(v0), p(t0), B,
+                                                   C.byref(bs[0]), C.byref(bs[1]), C.byref(prm), C.byref(out))
     if rc:
         raise _lib.IkgError(rc, "emulated per-state rollout")
     return res

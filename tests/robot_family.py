@@ -416,40 +416,3 @@ def frame_kinematics(cm, q, v, rf):
         out["dJ"][6 * h:6 * h + 6] = dJh
         out["dJv"][6 * h:6 * h + 6] = dJh @ v
     return out
-
-
-# ---------------------------------------------------------------- the host emulator (csrc/ikg_host_emu.hip)
-def load_emu(path):
-    import ctypes as C
-    lib = C.CDLL(path)
-    vp = C.c_void_p
-    lib.ikg_emu_solve.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp]
-    lib.ikg_emu_model_info.argtypes = [vp, vp]
-    return lib
-
-
-def model_info(lib, model):
-    import ctypes as C
-    from ikgrasp import _lib
-    out = (C.c_int32 * 8)()
-    desc = _lib.model_desc(model)
-    assert lib.ikg_emu_model_info(C.byref(desc), out) == 0
-    return dict(zip(INFO, list(out)))
-
-
-def emu_solve(lib, model, targets, q0, dtype=0, scene=None, **kw):
-    import ctypes as C
-    from ikgrasp import _lib
-    npt = np.float64 if dtype == 0 else np.float32
-    tg = np.ascontiguousarray(targets, dtype=npt).reshape(-1, 12)
-    B, nq = len(tg), model.nq
-    q0 = np.ascontiguousarray(q0, dtype=npt)
-    stride = 0 if q0.ndim == 1 else nq
-    desc = _lib.model_desc(model)
-    cd = _lib.collision_desc(scene) if scene is not None else None
-    p = _lib.default_params(check_collision=int(scene is not None), **kw)
-    q, conv, it, err = np.empty((B, nq), npt), np.empty(B, np.uint8), np.empty(B, np.int32), np.empty((B, 2), npt)
-    assert lib.ikg_emu_solve(C.byref(desc), dtype, tg.ctypes.data, q0.ctypes.data, stride, B, C.byref(p), q.ctypes.data,
-                             conv.ctypes.data, it.ctypes.data, err.ctypes.data, None, 0,
-                             C.byref(cd) if cd is not None else None) == 0
-    return q, conv.astype(bool), it, err

@@ -8,6 +8,7 @@ import os
 import numpy as np
 
 import dynamics_oracle as do
+import emu as host_emu
 from ikgrasp import _lib
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -70,33 +71,29 @@ def tolerances(d, name):
 
 # ---------------------------------------------------------------- the emulator behind IKSolver's methods
 class EmuSolver:
-    """ikg_emu_* (libikgrasp_emu.so) with the signatures of IKSolver.rollout /
+    """ikg_emu_* (libikgrasp_emu.so, tests/emu.py) with the signatures of IKSolver.rollout /
     forward_dynamics / bezier / control_torques, numpy only."""
 
-    def __init__(self, emu, model, inertias):
-        self.emu, self.model, self.nq = emu, model, model.nq
+    def __init__(self, model, inertias):
+        self.emu, self.model, self.inertias, self.nq = host_emu.load(), model, inertias, model.nq
         self.desc = _lib.model_desc(model)
         self.idesc = _lib.inertia_desc(inertias) if inertias is not None else None
 
     @staticmethod
     def _p(a):
-        return None if a is None else C.c_void_p(a.ctypes.data)
+        return None if a is None else a.ctypes.data
 
     def _rows(self, x, w=None):
         return None if x is None else np.ascontiguousarray(x, dtype=np.float64).reshape(-1, w or self.nq)
 
     def dynamics(self, q, v=None, outputs=("M", "nle")):
-        q, v = self._rows(q), self._rows(v)
-        M, nle = np.empty((len(q), self.nq, self.nq)), np.empty_like(q)
-        assert self.emu.ikg_emu_dynamics(C.byref(self.desc), C.byref(self.idesc), 0, self._p(q), self._p(v),
-                                         C.c_int64(len(q)), self._p(M), self._p(nle), None) == 0
-        return {"M": M, "nle": nle}
+        return host_emu.dynamics(self.model, self.inertias, q, v, outputs=("M", "nle"))
 
     def forward_dynamics(self, q, v, tau):
         q, v, tau = self._rows(q), self._rows(v), self._rows(tau)
         out = np.empty_like(q)
         rc = self.emu.ikg_emu_forward_dynamics(C.byref(self.desc), C.byref(self.idesc), self._p(q), self._p(v),
-                                               self._p(tau), C.c_int64(len(q)), self._p(out))
+                                               self._p(tau), len(q), self._p(out))
         if rc:
             raise _lib.IkgError(rc, "emulated forward dynamics")
         return out
@@ -105,8 +102,8 @@ class EmuSolver:
         pts, t_min, t_max, mult = _lib.curve((points, t_min, t_max, mult))
         tt = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
         out = np.empty((len(tt), pts.shape[1]))
-        rc = self.emu.ikg_emu_bezier(self._p(pts), C.c_int32(pts.shape[0]), C.c_int32(pts.shape[1]), C.c_double(t_min),
-                                     C.c_double(t_max), C.c_double(mult), self._p(tt), C.c_int64(len(tt)), self._p(out))
+        rc = self.emu.ikg_emu_bezier(self._p(pts), pts.shape[0], pts.shape[1], float(t_min), float(t_max), float(mult),
+                                     self._p(tt), len(tt), self._p(out))
         if rc:
             raise _lib.IkgError(rc, "emulated bezier")
         return out
@@ -116,13 +113,8 @@ class EmuSolver:
         B, nq = q.shape
         J, dJv, e, ed = np.empty((B, 12, nq)), np.empty((B, 12)), np.empty((B, 12)), np.empty((B, 12))
         assert self.emu.ikg_emu_frame_terms(C.byref(self.desc), self._p(q), self._p(v), self._p(qd), self._p(vd),
-                                            C.c_int64(B), self._p(J), self._p(dJv), self._p(e), self._p(ed)) == 0
-        prm = _lib.control_params(**gains)
-        tau = np.empty((B, nq))
-        assert self.emu.ikg_emu_control_torque(C.byref(self.desc), C.byref(self.idesc), self._p(q), self._p(v),
-                                               self._p(J), self._p(dJv), self._p(e), self._p(ed), C.c_int64(B),
-                                               C.byref(prm), self._p(tau), None, None, None, None) == 0
-        return {"tau": tau}
+                                            B, self._p(J), self._p(dJv), self._p(e), self._p(ed)) == 0
+        return host_emu.control_torque(self.model, self.inertias, q, v, J, dJv, e, ed, outputs=("tau",), **gains)
 
     def rollout(self, q0, v0, trajs, t0=None, ticks=0, dt_sim=1e-3, dt_traj=1e-2, record_every=0,
                 outputs=("q", "v", "t"), **gains):
@@ -139,8 +131,7 @@ class EmuSolver:
         out = _lib.RolloutOut(*[None if k not in res else res[k].ctypes.data
                                 for k in ("q", "v", "t", "q_hist", "v_hist", "tau_hist")])
         rc = self.emu.ikg_emu_control_rollout(C.byref(self.desc), C.byref(self.idesc), self._p(q0), self._p(v0),
-                                              self._p(t0), C.c_int64(B), C.byref(bq), C.byref(bv), C.byref(prm),
-                                              C.byref(out))
+                                              self._p(t0), B, C.byref(bq), C.byref(bv), C.byref(prm), C.byref(out))
         if rc:
             raise _lib.IkgError(rc, "emulated rollout")
         return res

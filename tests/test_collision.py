@@ -23,7 +23,7 @@ import os
 
 import numpy as np
 
-import helpers
+import emu as host_emu
 import pytest
 
 from conftest import GOLDEN
@@ -31,8 +31,6 @@ from ikgrasp import _lib
 from ikgrasp.collision import load_nextage_scene
 from ikgrasp.model import load_nextage
 from oracle import collision_oracle as co
-
-EMU = helpers.emu_path()
 
 
 @pytest.fixture(scope="module")
@@ -52,37 +50,15 @@ def solve_cases():
 
 @pytest.fixture(scope="module")
 def emu():
-    if not os.path.exists(EMU):
-        pytest.skip("libikgrasp_emu.so not built")
-    lib = C.CDLL(EMU)
-    vp = C.c_void_p
-    lib.ikg_emu_solve.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp]
-    lib.ikg_emu_collision.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int64, vp]
-    md = _lib.model_desc(load_nextage())
-    cd = _lib.collision_desc(load_nextage_scene())
+    host_emu.load_or_skip()
+    model, scene = load_nextage(), load_nextage_scene()
 
     def collision(q, targets, dtype=0):
-        npt = np.float64 if dtype == 0 else np.float32
-        q = np.ascontiguousarray(q, dtype=npt).reshape(-1, 15)
-        tg = np.ascontiguousarray(targets, dtype=npt).reshape(-1, 12)
-        out = np.empty(len(q), np.uint8)
-        lib.ikg_emu_collision(C.byref(md), C.byref(cd), dtype, q.ctypes.data, tg.ctypes.data, len(q),
-                              out.ctypes.data)
-        return out.astype(bool)
+        return host_emu.collision(model, scene, q, targets, dtype)
 
-    def solve(targets, q0, dtype=0, **kw):
-        npt = np.float64 if dtype == 0 else np.float32
-        tg = np.ascontiguousarray(targets, dtype=npt).reshape(-1, 12)
-        B = len(tg)
-        q0 = np.ascontiguousarray(np.broadcast_to(q0, (B, 15)), dtype=npt)
-        p = _lib.default_params(**kw)
-        q = np.empty((B, 15), npt)
-        conv = np.empty(B, np.uint8)
-        it = np.empty(B, np.int32)
-        err = np.empty((B, 2), npt)
-        assert 0 == lib.ikg_emu_solve(C.byref(md), dtype, tg.ctypes.data, q0.ctypes.data, 15, B, C.byref(p), q.ctypes.data,
-                          conv.ctypes.data, it.ctypes.data, err.ctypes.data, None, 0, C.byref(cd))
-        return q, conv.astype(bool), it, err
+    def solve(targets, q0, dtype=0, **kw):  # a q0 row per problem
+        B = len(np.reshape(targets, (-1, 12)))
+        return host_emu.solve(model, targets, np.broadcast_to(q0, (B, 15)), dtype, scene=scene, **kw)
 
     return collision, solve
 
@@ -268,9 +244,7 @@ def test_ball_certificate_is_sound(col_cases, oscene, dtype):
     oracle's own narrow phase (oracle/collision_oracle.py collide).  The
     certificate must also cover most small perturbations (it exists to skip
     narrow phases)."""
-    lib = C.CDLL(EMU)
-    vp = C.c_void_p
-    lib.ikg_emu_ball_cert.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int64, vp, vp]
+    lib = host_emu.load()
     md = _lib.model_desc(load_nextage())
     scene = load_nextage_scene()
     cd = _lib.collision_desc(scene)
@@ -289,21 +263,21 @@ def test_ball_certificate_is_sound(col_cases, oscene, dtype):
             scales = np.repeat([1e-5, 1e-4, 1e-3, 1e-2], 8)
             dq = rng.uniform(-1, 1, (len(scales), 15)) * scales[:, None]
             qs = np.ascontiguousarray(q[None] + dq, dtype=npt)
-            r = C.c_double()
+            r = np.empty(1)
             cov = np.empty(len(qs), np.uint8)
             qc = np.ascontiguousarray(q, dtype=npt)
             tgc = np.ascontiguousarray(tg, dtype=npt)
             assert lib.ikg_emu_ball_cert(C.byref(md), C.byref(cd), dtype, index[(a, b)], qc.ctypes.data,
-                                         tgc.ctypes.data, qs.ctypes.data, len(qs), C.byref(r),
+                                         tgc.ctypes.data, qs.ctypes.data, len(qs), r.ctypes.data,
                                          cov.ctypes.data) == 0
-            if r.value > 0:
+            if r[0] > 0:
                 n_cert += 1
             n_small += 8
             n_small_cov += int(cov[:8].sum())
             for k in np.nonzero(cov)[0]:
                 n_cov += 1
                 P = co.geom_poses(oscene, qs[k].astype(np.float64), TR, Tt)
-                assert co.collide(gs[a], P[a][0], P[a][1], gs[b], P[b][0], P[b][1]), (i, a, b, k, r.value)
+                assert co.collide(gs[a], P[a][0], P[a][1], gs[b], P[b][0], P[b][1]), (i, a, b, k, r[0])
     print(f"dtype {dtype}: {n_pairs} colliding pairs, {n_cert} certified, {n_cov} perturbed configurations "
           f"proved (all confirmed), 1e-5 perturbations covered {n_small_cov}/{n_small}")
     assert n_pairs >= 40 and n_cert >= 0.8 * n_pairs

@@ -3,12 +3,9 @@
 the support function of A - B sampled by the collision oracle.  The bound
 must never exceed the depth (it licenses skipping checks: the answer must not
 change), and should be close to it."""
-import ctypes as C
-import os
-
 import numpy as np
 
-import helpers
+import emu as host_emu
 import pytest
 
 from ikgrasp import _lib
@@ -17,20 +14,15 @@ from oracle import collision_oracle as co
 
 @pytest.fixture(scope="module")
 def epa():
-    path = helpers.emu_path()
-    if not os.path.exists(path):
-        pytest.skip("libikgrasp_emu.so not built")
-    lib = C.CDLL(path)
-    dp = C.POINTER(C.c_double)
-    lib.ikg_emu_epa.argtypes = [C.c_int, dp, dp, dp, C.c_int, dp, dp, dp, C.POINTER(C.c_int), dp]
+    lib = host_emu.load_or_skip()
 
     def run(ga, Ra, ta, gb, Rb, tb):
         arr = lambda x: np.ascontiguousarray(x, dtype=np.float64)
         Ra, ta, da, Rb, tb, db = map(arr, (Ra, ta, ga["dims"], Rb, tb, gb["dims"]))
-        p = lambda x: x.ctypes.data_as(dp)
-        r, d = C.c_int(), C.c_double()
-        lib.ikg_emu_epa(ga["kind"], p(Ra), p(ta), p(da), gb["kind"], p(Rb), p(tb), p(db), C.byref(r), C.byref(d))
-        return r.value, d.value
+        p = lambda x: x.ctypes.data
+        r, d = np.empty(1, np.int32), np.empty(1)
+        lib.ikg_emu_epa(ga["kind"], p(Ra), p(ta), p(da), gb["kind"], p(Rb), p(tb), p(db), p(r), p(d))
+        return int(r[0]), float(d[0])
 
     return run
 

@@ -14,8 +14,9 @@ import numpy as np
 import pytest
 
 import dynamics_oracle as do
+import emu as host_emu
 from conftest import GOLDEN, ROOT
-from helpers import emu_path, fk_tables
+from helpers import fk_tables
 from ikgrasp import _lib
 from ikgrasp.model import (BodyInertias, DualArmModel, load_nextage, load_nextage_inertia, parse_urdf, rpy_to_matrix,
                            sym6_matrix)
@@ -44,7 +45,7 @@ def tilted():
 
 @pytest.fixture(scope="module")
 def emu():
-    return C.CDLL(emu_path())
+    return host_emu.load()
 
 
 # ---------------------------------------------------------------- inertia compile
@@ -236,26 +237,14 @@ def test_controller_restatement_properties(dc, nextage):
 
 
 # ---------------------------------------------------------------- the kernels' arithmetic on the host
-def _emu_dynamics(emu, model, bi, q, v, dt):
-    d, idd = _lib.model_desc(model), _lib.inertia_desc(bi)
-    B, nq = q.shape
-    q, v = np.ascontiguousarray(q, dtype=dt), np.ascontiguousarray(v, dtype=dt)
-    M, n, g = np.empty((B, nq, nq), dt), np.empty((B, nq), dt), np.empty((B, nq), dt)
-    vp = lambda a: C.c_void_p(a.ctypes.data)
-    rc = emu.ikg_emu_dynamics(C.byref(d), C.byref(idd), 0 if dt == np.float64 else 1, vp(q), vp(v), C.c_int64(B),
-                              vp(M), vp(n), vp(g))
-    assert rc == 0
-    return {"M": M, "nle": n, "g": g}
-
-
 @pytest.mark.parametrize("which", ["nextage", "tilted"])
 def test_emulated_dynamics_match_fixtures(emu, dc, nextage, tilted, which):
     if which == "nextage":
         model, bi, pre, q, v = nextage[0], nextage[1], "", dc["q"], dc["v"]
     else:
         model, bi, pre, q, v = tilted[0], tilted[1], "tilted_", dc["tilted_q"], dc["tilted_v"]
-    r64 = _emu_dynamics(emu, model, bi, q, v, np.float64)
-    r32 = _emu_dynamics(emu, model, bi, q, v, np.float32)
+    r64 = host_emu.dynamics(model, bi, q, v, 0)
+    r32 = host_emu.dynamics(model, bi, q, v, 1)
     for k in ("M", "nle", "g"):
         ref = dc[pre + k]
         e64 = np.abs(r64[k] - ref).max() / np.abs(ref).max()
@@ -266,23 +255,13 @@ def test_emulated_dynamics_match_fixtures(emu, dc, nextage, tilted, which):
     assert np.array_equal(r64["M"], r64["M"].transpose(0, 2, 1))
 
 
-def _emu_control(emu, model, bi, dc, n, **gains):
-    d, idd = _lib.model_desc(model), _lib.inertia_desc(bi)
-    prm = _lib.control_params(**gains)
-    nq = model.nq
-    out = {"tau": np.empty((n, nq)), "qdd": np.empty((n, nq)), "xdd": np.empty((n, 12)), "Lambda": np.empty((n, 2, 36)),
-           "fc": np.empty((n, 12))}
-    vp = lambda a: C.c_void_p(np.ascontiguousarray(a[:n], dtype=np.float64).ctypes.data)
-    ins = [np.ascontiguousarray(dc[k][:n], dtype=np.float64) for k in ("q", "v", "J", "dJv", "err", "derr")]
-    rc = emu.ikg_emu_control_torque(C.byref(d), C.byref(idd), *[C.c_void_p(a.ctypes.data) for a in ins], C.c_int64(n),
-                                    C.byref(prm), *[C.c_void_p(out[k].ctypes.data) for k in CTL])
-    assert rc == 0
-    return out
+def _emu_control(model, bi, dc, n, **gains):
+    return host_emu.control_torque(model, bi, *(dc[k][:n] for k in host_emu.CONTROL_IN), **gains)
 
 
 def test_emulated_control_solve_within_measured_bounds(emu, dc, nextage):
     model, bi, _ = nextage
-    r = _emu_control(emu, model, bi, dc, 96)
+    r = _emu_control(model, bi, dc, 96)
     for k in CTL:
         ref = dc[k + "_mp"]
         err = np.abs(r[k] - ref).max() / np.abs(ref).max()
@@ -294,8 +273,8 @@ def test_emulated_control_solve_within_measured_bounds(emu, dc, nextage):
 def test_emulated_control_solve_honours_gains(emu, dc, nextage):
     model, bi, _ = nextage
     g = dict(zip(("Kp", "Kv", "Kf", "Kt", "lambda_reg", "qp_reg"), dc["gains_alt"]))
-    r = _emu_control(emu, model, bi, dc, 8, fc_bias=dc["fc_bias_alt"], **g)
-    base = _emu_control(emu, model, bi, dc, 8)
+    r = _emu_control(model, bi, dc, 8, fc_bias=dc["fc_bias_alt"], **g)
+    base = _emu_control(model, bi, dc, 8)
     for k in CTL:
         ref = dc[k + "_alt_mp"]
         assert np.abs(r[k] - ref).max() <= float(dc["tol_" + k]) * np.abs(ref).max(), k

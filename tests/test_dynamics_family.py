@@ -10,16 +10,15 @@ tables (anc, levels, ref, grav) are right -- where nothing depends on a GPU.
 Bounds: fp64 M / nle / g 1e-12 x max(1, max|fixture|); fp32 tol32_<out>
 (8 x the float32 oracle's largest error on any model); controller outputs
 tol_<out> (20 x the float64 restatement's error against 50 digits)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import dynamics_family_cases as fc
 import dynamics_oracle as do
+import emu as host_emu
 import robot_family as rf
-from helpers import emu_path, report
-from test_dynamics import _emu_control, _emu_dynamics
+from helpers import report
+from test_dynamics import _emu_control
 
 DYN, CTL = fc.DYN, fc.CTL
 NQ = {"nx_scaled": 13, "nx_extra_zero": 16, "mixed_axes": 32, "mixed_17": 17, "mixed_deep": 32}  # the others: 15
@@ -33,7 +32,7 @@ def cases():
 
 @pytest.fixture(scope="module")
 def emu():
-    return C.CDLL(emu_path())
+    return host_emu.load()
 
 
 # ---------------------------------------------------------------- the models
@@ -124,8 +123,8 @@ def test_fixture_properties(cases, name):
 def test_emulated_dynamics_match_fixture(emu, cases, name):
     model, bi = fc.models()[name]
     c = cases[name]
-    r64 = _emu_dynamics(emu, model, bi, c["q"], c["v"], np.float64)
-    r32 = _emu_dynamics(emu, model, bi, c["q"], c["v"], np.float32)
+    r64 = host_emu.dynamics(model, bi, c["q"], c["v"], 0)
+    r32 = host_emu.dynamics(model, bi, c["q"], c["v"], 1)
     row = {}
     for k in DYN:
         ref = c[k]
@@ -145,7 +144,7 @@ def test_emulated_dynamics_match_fixture(emu, cases, name):
 def test_emulated_control_solve_within_measured_bounds(emu, cases, name):
     model, bi = fc.models()[name]
     c = cases[name]
-    r = _emu_control(emu, model, bi, c, fc.N_STATES)
+    r = _emu_control(model, bi, c, fc.N_STATES)
     row = {k: {"err": np.abs(r[k] - c[k + "_mp"]).max() / np.abs(c[k + "_mp"]).max(), "restatement": c["err_f64_" + k],
                "bound": c["tol_" + k]} for k in CTL}
     report(f"control_family_emu_{name}", row)

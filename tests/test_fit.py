@@ -16,7 +16,6 @@ import pytest
 import fit_cases as fc
 import fit_oracle as fo
 import rollout_cases as rc
-from helpers import emu_path
 from ikgrasp import _lib, control
 
 
@@ -26,13 +25,8 @@ def d():
 
 
 @pytest.fixture(scope="module")
-def emu():
-    return C.CDLL(emu_path())
-
-
-@pytest.fixture(scope="module")
-def fitter(emu):
-    return fc.EmuFit(emu)
+def fitter():
+    return fc.EmuFit()
 
 
 @pytest.fixture(scope="module")
@@ -41,9 +35,9 @@ def rd():
 
 
 @pytest.fixture(scope="module")
-def nextage(emu):
+def nextage():
     m, bi = rc.models()["nextage"]
-    return rc.EmuSolver(emu, m, bi)
+    return rc.EmuSolver(m, bi)
 
 
 # ---------------------------------------------------------------- the fit against 50 digits

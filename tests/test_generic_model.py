@@ -4,18 +4,16 @@ compiled onto canonical axes by re-expressing joint frames (ikgrasp/model.py),
 checked against oracle/generic_oracle.py (raw axes, Rodrigues) on the
 synthetic robot tests/golden/tilted_dualarm.urdf, and the kernel arithmetic
 (host emulator, generic path) against the oracle's IK fixtures."""
-import ctypes as C
 import os
 import xml.etree.ElementTree as ET
 
 import numpy as np
 
-import helpers
+import emu as host_emu
 import pytest
 
 from conftest import GOLDEN
 from helpers import fk_tables, hands_from_tables
-from ikgrasp import _lib
 from ikgrasp.collision import _link_geoms, _robot_link_frames
 from ikgrasp.model import DualArmModel, axis_frame, parse_urdf
 from oracle import generic_oracle as go
@@ -93,20 +91,8 @@ def test_emulated_kernel_solves_tilted_robot(model, gc, variant):
     specialisation -- the tilted robot's wrist joints meet in a point, so the
     decoupled wrist solve (SpecGenericWrist); 99: forced SpecGeneric, the 6x6
     Householder QR."""
-    emu = helpers.emu_path()
-    if not os.path.exists(emu):
-        pytest.skip("libikgrasp_emu.so not built")
-    lib = C.CDLL(emu)
-    vp = C.c_void_p
-    lib.ikg_emu_solve.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp]
-    desc = _lib.model_desc(model)
-    tg, q0 = np.ascontiguousarray(gc["targets"]), np.ascontiguousarray(gc["q0"])
-    B = len(tg)
-    p = _lib.default_params()
-    p.variant = variant
-    q, conv, it, err = np.empty((B, model.nq)), np.empty(B, np.uint8), np.empty(B, np.int32), np.empty((B, 2))
-    assert lib.ikg_emu_solve(C.byref(desc), 0, tg.ctypes.data, q0.ctypes.data, model.nq, B, C.byref(p),
-                             q.ctypes.data, conv.ctypes.data, it.ctypes.data, err.ctypes.data, None, 0, None) == 0
+    host_emu.load_or_skip()
+    q, conv, it, err = host_emu.solve(model, gc["targets"], gc["q0"], variant=variant)
     ok = gc["converged"]
     assert np.array_equal(conv.astype(bool), ok) and np.array_equal(it, gc["iters"])
     assert np.abs(q[ok] - gc["q"][ok]).max() <= 1e-9

@@ -16,7 +16,7 @@ import time
 import numpy as np
 import pytest
 
-import helpers
+import emu as host_emu
 import robot_family as rf
 from helpers import se3_err
 
@@ -248,9 +248,8 @@ def test_collision_term_generic_qr(cases):
     m = rf.load_model(rf.COLLISION)
     scene = rf.collision_scene(m)
     c = cases[rf.COLLISION]
-    emu = rf.load_emu(helpers.emu_path())
-    q, conv, it, _ = rf.emu_solve(emu, m, c["targets"], c["q0"], scene=scene)
-    _, conv0, it0, _ = rf.emu_solve(emu, m, c["targets"], c["q0"])
+    q, conv, it, _ = host_emu.solve(m, c["targets"], c["q0"], scene=scene)
+    _, conv0, it0, _ = host_emu.solve(m, c["targets"], c["q0"])
     assert ((conv != conv0) | (it != it0)).sum() >= 3 and conv.sum() >= 3
     for which, spec in (("prebuilt", False), ("jit", "auto")):
         s = IKSolver(m, device=0, scene=scene, specialize=spec)

@@ -14,13 +14,10 @@ tests/test_gpu_rare_path.py (the host build does not contract products into FMAs
 bits are not the emulator's; tests/test_seam_stage_order.py compares the two forms' bits on the
 host, where both are compiled alike).  Measured on MI355X: max |q - emulator| 8.4e-15 (dt = 1),
 1.7e-15 and 1.0e-15; against the C oracle 1.3e-14, 2.8e-15, 1.7e-15."""
-import ctypes as C
-import os
-
 import numpy as np
 import pytest
 
-import helpers
+import emu as host_emu
 import rare_path_cases as rc
 from ikgrasp import _lib
 from ikgrasp.model import load_nextage
@@ -36,27 +33,14 @@ ROLLED = 5  # the rolled target's row
 
 
 def _emu_solve(tg, **kw):
-    lib = C.CDLL(helpers.emu_path())
-    vp = C.c_void_p
-    lib.ikg_emu_solve.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp]
-    desc = _lib.model_desc(load_nextage())
-    tg = np.ascontiguousarray(tg, dtype=np.float64).reshape(-1, 12)
-    B = len(tg)
-    q0 = np.zeros(15)
-    p = _lib.default_params(**kw)
-    q = np.empty((B, 15))
-    conv = np.empty(B, np.uint8)
-    it = np.empty(B, np.int32)
-    err = np.empty((B, 2))
-    assert 0 == lib.ikg_emu_solve(C.byref(desc), 0, tg.ctypes.data, q0.ctypes.data, 0, B, C.byref(p), q.ctypes.data,
-                                  conv.ctypes.data, it.ctypes.data, err.ctypes.data, None, 0, None)
-    return q, conv.astype(bool), it, err, desc
+    model = load_nextage()
+    return host_emu.solve(model, tg, np.zeros(15), **kw) + (_lib.model_desc(model),)
 
 
 @pytest.fixture(scope="module")
 def cases():
     """name -> targets [33, 12], solve parameters, the emulator's and the C oracle's answers"""
-    assert os.path.exists(helpers.emu_path()), "libikgrasp_emu.so not built"
+    host_emu.load()
     from oracle import c_oracle
     base = uniform_targets(64, seed=3)[:33]
     above = base.copy()

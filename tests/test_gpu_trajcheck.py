@@ -26,7 +26,6 @@ At most 8 x 33 single-wave checks per call.
 import numpy as np
 import pytest
 
-import helpers
 import trajcheck_cases as tc
 
 pytestmark = pytest.mark.gpu
@@ -193,7 +192,7 @@ def test_generic_robot_device_equals_emulator():
     pair_idx = np.array([k for k, (_, b) in enumerate(scene.pairs) if b == table], dtype=np.int32)
     assert len(pair_idx) > 0
     fixed = np.tile(np.concatenate([np.eye(3).reshape(9), rf.grasp_center(rf.COLLISION)]), (3, 1))
-    emu = tc.emu_runner(m, scene, helpers.emu_path())
+    emu = tc.emu_runner(m, scene)
     s = IKSolver(m, device=0, scene=scene, specialize=False)
     b = tc.bounds()
     for cube in (None, fixed):

@@ -23,7 +23,6 @@ At most 3 x 33 samples per call.
 import numpy as np
 import pytest
 
-import helpers
 import trajdyn_oracle as to
 
 pytestmark = pytest.mark.gpu
@@ -172,7 +171,7 @@ def test_dyntraj_and_retime_on_fitted_trajectories(robot):
 
 def test_family_robot_device_equals_emulator(run, answers):
     cs = to.case("family")
-    emu = to.emu_runner(*to.model_of("mixed_17"), helpers.emu_path())
+    emu = to.emu_runner(*to.model_of("mixed_17"))
     want = emu(*to.inputs(cs))
     got = answers["family"]
     for k in to.SAMPLE + to.RATIOS:

@@ -3,47 +3,29 @@ the exact stage functions of ikg_device.hpp composed for both arm lanes).
 This is test tooling, not the product path; it lets the CPU suite cover the
 specialised (spherical-wrist, compile-time axes) and generic (runtime axes,
 Householder QR) solves against the oracle fixtures without a GPU."""
-import ctypes as C
 import os
 
 import numpy as np
 
-import helpers
+import emu as host_emu
 import pytest
 
-from ikgrasp import _lib
 from ikgrasp.model import load_nextage
 
-EMU = helpers.emu_path()
 GENERIC = 99  # ikg_params.variant value the emulator reads as "force the generic path"
 
 
 @pytest.fixture(scope="module")
 def emu():
-    if not os.path.exists(EMU):
-        pytest.skip("libikgrasp_emu.so not built")
-    lib = C.CDLL(EMU)
-    vp = C.c_void_p
-    lib.ikg_emu_solve.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp]
-    desc = _lib.model_desc(load_nextage())
+    host_emu.load_or_skip()
+    model = load_nextage()
 
     def solve(targets, q0, dtype=0, broadcast=False, **kw):
-        npt = np.float64 if dtype == 0 else np.float32
-        tg = np.ascontiguousarray(targets, dtype=npt).reshape(-1, 12)
-        B = len(tg)
         # per-row q0 (stride 15) runs the kernels' medium-range trig series, a
         # broadcast q0 (stride 0) the short series with the exact fallback
         # (fp64; fp32 takes the medium-range series either way)
-        q0 = np.ascontiguousarray(q0 if broadcast else np.broadcast_to(q0, (B, 15)), dtype=npt)
-        stride = 0 if broadcast else 15
-        p = _lib.default_params(**kw)
-        q = np.empty((B, 15), npt)
-        conv = np.empty(B, np.uint8)
-        it = np.empty(B, np.int32)
-        err = np.empty((B, 2), npt)
-        assert 0 == lib.ikg_emu_solve(C.byref(desc), dtype, tg.ctypes.data, q0.ctypes.data, stride, B, C.byref(p), q.ctypes.data,
-                          conv.ctypes.data, it.ctypes.data, err.ctypes.data, None, 0, None)
-        return q, conv.astype(bool), it, err
+        B = len(np.reshape(targets, (-1, 12)))
+        return host_emu.solve(model, targets, q0 if broadcast else np.broadcast_to(q0, (B, 15)), dtype, **kw)
 
     return solve
 
@@ -106,32 +88,21 @@ def test_medium_trig_series_matches_exact_fallback(emu, dtype):
             assert np.array_equal(a[0], b[0])
 
 
-def _emu_math(fn, x, y=None):
-    lib = C.CDLL(EMU)
-    lib.ikg_emu_math.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    x = np.ascontiguousarray(x, dtype=np.float64)
-    y = np.ascontiguousarray(x if y is None else y, dtype=np.float64)
-    out = np.empty(2 * len(x), dtype=np.float64)
-    assert lib.ikg_emu_math(fn, len(x), x.ctypes.data, y.ctypes.data, out.ctypes.data) == 0
-    return out
-
-
 def test_loop_math_accuracy():
     """The loop's own math (ikg_device.hpp): Cody-Waite sincos within 2 ulp
     (fp64) / 2 ulp of float (fp32) over the joint range and beyond, and the
     packed pair's atan2_upper within 1.5 float ulps of pi (3.6e-7) over the
     upper half plane (host arithmetic: exact division instead of the device's
     reciprocal refinement)."""
-    if not os.path.exists(EMU):
-        pytest.skip("libikgrasp_emu.so not built")
+    host_emu.load_or_skip()
     rng = np.random.default_rng(7)
     x = np.concatenate([rng.uniform(-8, 8, 20000), np.linspace(-np.pi, np.pi, 4001), [0.0, 1e-300, -1e-300]])
-    o = _emu_math(0, x).reshape(-1, 2)
+    o = host_emu.math(0, x).reshape(-1, 2)
     assert np.abs(o[:, 0] - np.sin(x)).max() <= 2 * np.spacing(1.0)
     assert np.abs(o[:, 1] - np.cos(x)).max() <= 2 * np.spacing(1.0)
     xf = x.astype(np.float32).astype(np.float64)
     for fn in (1, 2):
-        o = _emu_math(fn, xf).reshape(-1, 2)
+        o = host_emu.math(fn, xf).reshape(-1, 2)
         assert np.abs(o[:, 0] - np.sin(xf)).max() <= 2 * float(np.spacing(np.float32(1.0)))
         assert np.abs(o[:, 1] - np.cos(xf)).max() <= 2 * float(np.spacing(np.float32(1.0)))
     th = np.concatenate([rng.uniform(0, np.pi, 20000), [0.0, np.pi / 4, np.pi / 2, np.pi, 1e-6, np.pi - 1e-6]])
@@ -139,7 +110,7 @@ def test_loop_math_accuracy():
     yy = (r * np.sin(th)).astype(np.float32).astype(np.float64)
     xx = (r * np.cos(th)).astype(np.float32).astype(np.float64)
     for fn in (3, 4):
-        a = _emu_math(fn, xx, yy)[:len(xx)]
+        a = host_emu.math(fn, xx, yy)[:len(xx)]
         assert np.abs(a - np.arctan2(yy, xx)).max() <= 1.5 * float(np.spacing(np.float32(np.pi)))
 
 

@@ -5,53 +5,25 @@ ikg_emu_force_small_angle(1) takes the branch on every update, as a lane does wh
 hold it taken, and every output must be the bits of the run that takes it only where the
 problem's own angle asks for it.  Counts against the C oracle, q within tests/test_host_emu.py's
 fp64 tolerance."""
-import ctypes as C
-import os
-
 import numpy as np
 import pytest
 
-import helpers
+import emu as host_emu
 import rare_path_cases as rc
-from ikgrasp import _lib
 from ikgrasp.model import load_nextage
 from ikgrasp.workload import uniform_targets
 
-EMU = helpers.emu_path()
 Q_TOL = 1e-9  # tests/test_host_emu.py
 
 
 @pytest.fixture(scope="module")
 def emu():
-    assert os.path.exists(EMU), "libikgrasp_emu.so not built (make -C csrc emu)"
-    lib = C.CDLL(EMU)
-    vp = C.c_void_p
-    lib.ikg_emu_solve.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp]
-    for f in (lib.ikg_emu_force_general, lib.ikg_emu_force_small_angle):
-        f.argtypes = [C.c_int]
-        f.restype = None
-    desc = _lib.model_desc(load_nextage())
+    host_emu.load()
+    model = load_nextage()
 
     def solve(targets, q0, general=False, small=False, **kw):
-        tg = np.ascontiguousarray(targets, dtype=np.float64).reshape(-1, 12)
-        B = len(tg)
-        q0 = np.ascontiguousarray(q0, dtype=np.float64)
-        stride = 0 if q0.ndim == 1 else 15
-        p = _lib.default_params(**kw)
-        q = np.empty((B, 15))
-        conv = np.empty(B, np.uint8)
-        it = np.empty(B, np.int32)
-        err = np.empty((B, 2))
-        lib.ikg_emu_force_general(1 if general else 0)
-        lib.ikg_emu_force_small_angle(1 if small else 0)
-        try:
-            assert 0 == lib.ikg_emu_solve(C.byref(desc), 0, tg.ctypes.data, q0.ctypes.data, stride, B, C.byref(p),
-                                          q.ctypes.data, conv.ctypes.data, it.ctypes.data, err.ctypes.data, None, 0,
-                                          None)
-        finally:
-            lib.ikg_emu_force_general(0)
-            lib.ikg_emu_force_small_angle(0)
-        return q, conv.astype(bool), it, err
+        with host_emu.forced(general=general, small_angle=small):
+            return host_emu.solve(model, targets, q0, **kw)
 
     return solve
 

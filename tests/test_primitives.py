@@ -22,13 +22,12 @@ IKG_EMU_LIB names another emulator build (helpers.emu_path): an emulator built
 from the new ikg_host_emu.hip against an older ikg_collision.hpp shows what
 that narrow phase gets wrong (tools/README.md, "Narrow phase at contact").
 """
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
-import helpers
+import emu as host_emu
 from conftest import GOLDEN
 
 from oracle import collision_oracle as co
@@ -43,12 +42,7 @@ def fx():
 
 @pytest.fixture(scope="module")
 def emu_pairs():
-    path = helpers.emu_path()
-    if not os.path.exists(path):
-        pytest.skip("libikgrasp_emu.so not built")
-    lib = C.CDLL(path)
-    dp, ip, bp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
-    lib.ikg_emu_pairs.argtypes = [C.c_int, C.c_int64, ip, dp, dp, ip, dp, dp, bp, dp, dp]
+    lib = host_emu.load_or_skip()
 
     def run(dtype, kA, PA, dA, kB, PB, dB):
         n = len(kA)
@@ -56,9 +50,7 @@ def emu_pairs():
         PA, dA, PB, dB = (np.ascontiguousarray(x, dtype=np.float64) for x in (PA, dA, PB, dB))
         hit = np.empty(n, dtype=np.uint8)
         d, dq = np.empty(n), np.empty(n)
-        p = lambda x, t: x.ctypes.data_as(t)
-        rc = lib.ikg_emu_pairs(0 if dtype == "f64" else 1, n, p(kA, ip), p(PA, dp), p(dA, dp), p(kB, ip), p(PB, dp),
-                               p(dB, dp), p(hit, bp), p(d, dp), p(dq, dp))
+        rc = lib.ikg_emu_pairs(0 if dtype == "f64" else 1, n, *[x.ctypes.data for x in (kA, PA, dA, kB, PB, dB, hit, d, dq)])
         assert rc == 0
         return hit.astype(bool), d, dq
 
@@ -227,25 +219,12 @@ def test_scene_collision_through_the_emulator(fx, dtype):
     bounding-sphere rejection of pair_hit lets the row's pair through (the
     diagonal vertex rows sit on its threshold) and drops the 47 others;
     geom_world composes the robot scene's placements."""
-    from ikgrasp import _lib
     from ikgrasp.model import load_nextage
-    path = helpers.emu_path()
-    if not os.path.exists(path):
-        pytest.skip("libikgrasp_emu.so not built")
-    lib = C.CDLL(path)
-    vp = C.c_void_p
-    lib.ikg_emu_collision.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int64, vp]
-    md = _lib.model_desc(load_nextage())
-    code, npt = (0, np.float64) if dtype == "f64" else (1, np.float32)
+    host_emu.load_or_skip()
+    model = load_nextage()
 
     def collision(scene, q, tg):
-        cd = _lib.collision_desc(scene)
-        q = np.ascontiguousarray(q, dtype=npt).reshape(-1, 15)
-        tg = np.ascontiguousarray(tg, dtype=npt).reshape(-1, 12)
-        out = np.empty(len(q), np.uint8)
-        assert lib.ikg_emu_collision(C.byref(md), C.byref(cd), code, q.ctypes.data, tg.ctypes.data, len(q),
-                                     out.ctypes.data) == 0
-        return out.astype(bool)
+        return host_emu.collision(model, scene, q, tg, 0 if dtype == "f64" else 1)
 
     idx, gap = sweep(fx)
     _, PB = placements(fx, idx, gap)

@@ -28,8 +28,8 @@ import os
 import numpy as np
 import pytest
 
+import emu as host_emu
 import projection_cases as pj
-from helpers import emu_path
 
 DELTA, TIE, EPS = 1e-9, 1e-6, 1e-3
 
@@ -56,10 +56,7 @@ class Emu:
         from ikgrasp import _lib
         from ikgrasp.collision import load_nextage_scene
         from ikgrasp.model import load_nextage
-        self.lib = C.CDLL(emu_path())
-        vp = C.c_void_p
-        self.lib.ikg_emu_project_paths.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_double, C.c_int32, vp, C.c_int32,
-                                                   vp, vp, vp, vp, vp, vp]
+        self.lib = host_emu.load()
         scene = load_nextage_scene()
         self.md, self.cd = _lib.model_desc(load_nextage()), _lib.collision_desc(scene)
         self.env = np.ascontiguousarray(scene.env_geoms(), dtype=np.int32)
@@ -74,13 +71,13 @@ class Emu:
         g = self.env if geoms is None else np.ascontiguousarray(geoms, dtype=np.int32)
         res = out or {"robot_path": np.empty((n, M, 15)), "cube_path": np.empty((n, M, 12)),
                       "n_nodes": np.empty(n, dtype=np.int32), "status": np.empty(n, dtype=np.int32)}
-        ran = C.c_int32(-1)
+        ran = np.full(1, -1, dtype=np.int32)
         rc = self.lib.ikg_emu_project_paths(C.byref(self.md), C.byref(self.cd), q0.ctypes.data, A.ctypes.data,
                                             B.ctypes.data, n, float(step_size), int(max_nodes), g.ctypes.data, g.size,
                                             C.byref(self.prm), res["robot_path"].ctypes.data,
                                             res["cube_path"].ctypes.data, res["n_nodes"].ctypes.data,
-                                            res["status"].ctypes.data, C.byref(ran))
-        self.steps_run = ran.value
+                                            res["status"].ctypes.data, ran.ctypes.data)
+        self.steps_run = int(ran[0])
         return rc, res
 
     def run(self, q0, A, B, step_size, max_nodes):

@@ -9,16 +9,15 @@ Tolerances (test_generic_model.py / test_gpu_generic.py): fp64 identical
 flags and update counts, converged q within 1e-9; fp32 identical flags,
 counts within +-2, hand SE(3) distance to the fp64 fixture <= 1e-4.  Every
 check prints its largest error."""
-import os
+import ctypes as C
 
 import numpy as np
 import pytest
 
-import helpers
+import emu as host_emu
 import robot_family as rf
 from helpers import fk_tables, hands_from_tables, se3_err
 from ikgrasp import _lib
-from robot_family import emu_solve, model_info
 
 GENERIC = 99  # ikg_params.variant the emulator reads as "force the generic path"
 
@@ -35,10 +34,14 @@ def models():
 
 @pytest.fixture(scope="module")
 def emu():
-    path = helpers.emu_path()
-    if not os.path.exists(path):
-        pytest.skip("libikgrasp_emu.so not built")
-    return rf.load_emu(path)
+    return host_emu.load_or_skip()
+
+
+def model_info(emu, model):
+    out = np.empty(8, np.int32)
+    desc = _lib.model_desc(model)
+    assert emu.ikg_emu_model_info(C.byref(desc), out.ctypes.data) == 0
+    return dict(zip(rf.INFO, out.tolist()))
 
 
 @pytest.mark.parametrize("name", rf.NAMES)
@@ -145,10 +148,10 @@ def _check64(name, leg, got, q_ref, conv_ref, it_ref):
 @pytest.mark.parametrize("name", rf.NAMES)
 def test_emulated_kernel_fp64(emu, models, cases, name, variant):
     m, c = models[name], cases[name]
-    _check64(name, f"fp64 variant {variant}", emu_solve(emu, m, c["targets"], c["q0"], variant=variant),
+    _check64(name, f"fp64 variant {variant}", host_emu.solve(m, c["targets"], c["q0"], variant=variant),
              c["q"], c["converged"], c["iters"])
     # the broadcast seed (short trig series with the exact fallback) on the cold cases
-    _check64(name, f"fp64 variant {variant} broadcast q0", emu_solve(emu, m, c["targets"][:8], np.zeros(m.nq), variant=variant),
+    _check64(name, f"fp64 variant {variant} broadcast q0", host_emu.solve(m, c["targets"][:8], np.zeros(m.nq), variant=variant),
              c["q"][:8], c["converged"][:8], c["iters"][:8])
 
 
@@ -156,7 +159,7 @@ def test_emulated_kernel_fp64(emu, models, cases, name, variant):
 @pytest.mark.parametrize("name", rf.DAMPED)
 def test_emulated_kernel_damped(emu, models, cases, name, variant):
     m, c = models[name], cases[name]
-    _check64(name, f"fp64 damped variant {variant}", emu_solve(emu, m, c["targets"], c["q0"], variant=variant, lam=1e-6),
+    _check64(name, f"fp64 damped variant {variant}", host_emu.solve(m, c["targets"], c["q0"], variant=variant, lam=1e-6),
              c["q_damped"], c["converged_damped"], c["iters_damped"])
 
 
@@ -164,7 +167,7 @@ def test_emulated_kernel_damped(emu, models, cases, name, variant):
 @pytest.mark.parametrize("name", rf.NAMES)
 def test_emulated_kernel_fp32(emu, models, cases, name, variant):
     m, c = models[name], cases[name]
-    q, conv, it, _ = emu_solve(emu, m, c["targets"], c["q0"], dtype=1, variant=variant)
+    q, conv, it, _ = host_emu.solve(m, c["targets"], c["q0"], dtype=1, variant=variant)
     ok = c["converged"].astype(bool)
     dit = int(np.abs(it[ok].astype(int) - c["iters"][ok]).max())
     h32 = np.array([hands_from_tables(m, x.astype(np.float64)) for x in q[ok]])
@@ -183,8 +186,8 @@ def test_collision_term_changes_answers(emu, models, cases):
     of the 24 cases in the emulator's answer (the GPU leg compares with it)."""
     m, c = models[rf.COLLISION], cases[rf.COLLISION]
     scene = rf.collision_scene(m)
-    _, conv0, it0, _ = emu_solve(emu, m, c["targets"], c["q0"])
-    _, conv1, it1, _ = emu_solve(emu, m, c["targets"], c["q0"], scene=scene)
+    _, conv0, it0, _ = host_emu.solve(m, c["targets"], c["q0"])
+    _, conv1, it1, _ = host_emu.solve(m, c["targets"], c["q0"], scene=scene)
     changed = (conv0 != conv1) | (it0 != it1)
     print(f"collision term: {int(changed.sum())} of 24 cases change; successes {int(conv1.sum())} (without: {int(conv0.sum())})")
     assert changed.sum() >= 3 and conv1.sum() >= 3

@@ -16,7 +16,6 @@ import pytest
 import dynamics_oracle as do
 import rollout_cases as rc
 import rollout_oracle as ro
-from helpers import emu_path
 from ikgrasp import _lib, control
 
 
@@ -32,8 +31,7 @@ def dc():
 
 @pytest.fixture(scope="module")
 def solvers():
-    emu = C.CDLL(emu_path())
-    return {name: rc.EmuSolver(emu, m, bi) for name, (m, bi) in rc.models().items()}
+    return {name: rc.EmuSolver(m, bi) for name, (m, bi) in rc.models().items()}
 
 
 @pytest.fixture(scope="module")

@@ -14,13 +14,11 @@ The projection's own bookkeeping (prepare / commit per chain, the step loop) on
 the emulator is tests/test_projection.py, on tests/golden/projection_cases.npz
 (tests/golden/make_projection_golden.py, tests/projection_cases.py).
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
+import emu as host_emu
 import rrt_cases as rc
-from helpers import emu_path
 
 STEP = 0.025
 
@@ -32,11 +30,7 @@ def cases():
 
 @pytest.fixture(scope="module")
 def emu():
-    lib = C.CDLL(emu_path())
-    vp = C.c_void_p
-    lib.ikg_emu_se3_interpolate.argtypes = [vp, vp, vp, C.c_int64, vp]
-    lib.ikg_emu_nearest.argtypes = [vp, C.c_int64, vp, vp, C.c_int32, C.c_int64, vp, vp]
-    return lib
+    return host_emu.load()
 
 
 def emu_nearest(lib, nodes, counts, queries):
@@ -181,10 +175,8 @@ def test_recorded_nearest_indices_follow_the_lowest_index_rule(cases):
 
 def test_emulator_interpolate_matches_50_digits(cases, emu):
     c = cases
-    A, B = np.ascontiguousarray(c["interp_A"]), np.ascontiguousarray(c["interp_B"])
-    al = np.ascontiguousarray(c["interp_alpha"])
-    out = np.empty_like(A)
-    assert emu.ikg_emu_se3_interpolate(A.ctypes.data, B.ctypes.data, al.ctypes.data, len(A), out.ctypes.data) == 0
+    A, B, al = c["interp_A"], c["interp_B"], c["interp_alpha"]
+    out = host_emu.se3_interpolate(A, B, al)
     err = np.abs(out - c["interp_exact"]).max(axis=1)
     bound = np.maximum(16 * c["interp_err"], 1e-15)
     print("interpolate: emulator error", err.tolist(), "bound", bound.tolist())

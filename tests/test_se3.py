@@ -28,17 +28,15 @@ theta / (|skew|/2) with the acos angle and carry an envelope on top
 Three shortcomings of log6_iter that this file found are pinned by strict xfails, each with
 a passing test next to it that holds it to its size.
 """
-import ctypes as C
 import math
-import os
 
 import numpy as np
 import pytest
 
+import emu as host_emu
 import helpers
 import se3_oracle as so
 
-EMU = helpers.emu_path()
 EPS = so.EPS["f64"]
 RESYNC64 = 128  # Trig<double>::kResync (ikg_device.hpp)
 KINC_ASIN = 0.035  # ThetaInc<double>::kIncAsin
@@ -56,11 +54,7 @@ TRACKED = {"E4-quad": 5, "E4-pair": 6, "E4-pair-z": 7}
 
 @pytest.fixture(scope="module")
 def emu():
-    if not os.path.exists(EMU):
-        pytest.skip("libikgrasp_emu.so not built")
-    lib = C.CDLL(EMU)
-    lib.ikg_emu_se3.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.ikg_emu_se3_interpolate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    lib = host_emu.load_or_skip()
 
     def run(fn, M, prev=None, width=6):
         M = np.ascontiguousarray(M, dtype=np.float64).reshape(-1, 12)
@@ -70,13 +64,7 @@ def emu():
         assert rc == 0, f"ikg_emu_se3({fn}) returned {rc}" + (": the packed halves differ" if rc == -2 else "")
         return out
 
-    def interpolate(A, B, alpha):
-        A, B, alpha = (np.ascontiguousarray(x, dtype=np.float64) for x in (A, B, alpha))
-        out = np.empty_like(A)
-        assert lib.ikg_emu_se3_interpolate(A.ctypes.data, B.ctypes.data, alpha.ctypes.data, len(A), out.ctypes.data) == 0
-        return out
-
-    run.interpolate = interpolate
+    run.interpolate = host_emu.se3_interpolate
     return run
 
 

@@ -11,16 +11,14 @@ without a resync, over
   * (s, c) at 0, pi/2, pi and random angles;
   * joints that land below, on and above either limit (dt = 1 and dt = 0.01)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
-import helpers
+import emu as host_emu
 from ikgrasp import _lib
 from ikgrasp.model import load_nextage
 
-EMU = helpers.emu_path()
 KINC = 0.025  # Trig<double>::kIncMax
 STEPS = [0.0, 1e-300, -1e-300, 1e-9, -1e-9, KINC, -KINC, np.nextafter(KINC, 0), -np.nextafter(KINC, 0),
          KINC * (1 - 1e-9), -KINC * (1 - 1e-9), 0.0212, -0.02, np.nextafter(KINC, 1), -np.nextafter(KINC, 1), 0.1]
@@ -28,10 +26,7 @@ STEPS = [0.0, 1e-300, -1e-300, 1e-9, -1e-9, KINC, -KINC, np.nextafter(KINC, 0), 
 
 @pytest.fixture(scope="module")
 def seam():
-    assert os.path.exists(EMU), "libikgrasp_emu.so not built (make -C csrc emu)"
-    lib = C.CDLL(EMU)
-    vp = C.c_void_p
-    lib.ikg_emu_seam.argtypes = [vp, C.c_int, C.c_int64, vp, C.c_double, vp, vp, vp]
+    lib = host_emu.load()
     desc = _lib.model_desc(load_nextage())
     lo = np.array([[desc.lower[desc.root_q]] + [desc.lower[desc.arm_q[a][k]] for k in range(6)] for a in range(2)])
     hi = np.array([[desc.upper[desc.root_q]] + [desc.upper[desc.arm_q[a][k]] for k in range(6)] for a in range(2)])

@@ -17,18 +17,15 @@ result is off the exact one by up to 1.3 rad (LAPACK rounding amplified by
 cond(J); on the first step it puts 79 rad into the exactly-zero head
 columns), so no implementation can match it there bit for bit.
 """
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
+import emu as host_emu
 import helpers
 from conftest import GOLDEN
-from ikgrasp import _lib
 from ikgrasp.model import load_nextage
-
-EMU = helpers.emu_path()
 
 
 @pytest.fixture(scope="module")
@@ -38,31 +35,9 @@ def sing():
 
 @pytest.fixture(scope="module")
 def emu():
-    if not os.path.exists(EMU):
-        pytest.skip("libikgrasp_emu.so not built")
-    lib = C.CDLL(EMU)
-    vp = C.c_void_p
-    lib.ikg_emu_solve.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp]
-    lib.ikg_emu_lq_count.restype = C.c_longlong
-    lib.ikg_emu_svd_count.restype = C.c_longlong
-    desc = _lib.model_desc(load_nextage())
-
-    def solve(targets, q0, dtype=0):
-        npt = np.float64 if dtype == 0 else np.float32
-        tg = np.ascontiguousarray(targets, dtype=npt)
-        B = len(tg)
-        q0 = np.ascontiguousarray(q0, dtype=npt)
-        p = _lib.default_params()
-        q = np.empty((B, 15), npt)
-        conv = np.empty(B, np.uint8)
-        it = np.empty(B, np.int32)
-        err = np.empty((B, 2), npt)
-        assert 0 == lib.ikg_emu_solve(C.byref(desc), dtype, tg.ctypes.data, q0.ctypes.data, 15, B, C.byref(p), q.ctypes.data,
-                          conv.ctypes.data, it.ctypes.data, err.ctypes.data, None, 0, None)
-        return q, conv.astype(bool), it
-
-    solve.lib = lib
-    return solve
+    host_emu.load_or_skip()
+    model = load_nextage()
+    return lambda targets, q0, dtype=0: host_emu.solve(model, targets, q0, dtype)[:3]
 
 
 def tol_exact(cond0):
@@ -90,11 +65,11 @@ def test_numpy_oracle_equals_exact_pinv_where_j_is_well_conditioned(sing):
 
 def test_emulated_kernel_matches_pinv_at_singularities(emu, sing):
     c = sing
-    emu.lib.ikg_emu_lq_count(1)
-    emu.lib.ikg_emu_svd_count(1)
+    host_emu.counter("lq")
+    host_emu.counter("svd")
     q, conv, it = emu(c["targets"], c["q0"])
-    assert emu.lib.ikg_emu_lq_count(1) >= 16  # the guard took the LQ form
-    assert emu.lib.ikg_emu_svd_count(1) >= 2  # and the Jacobi form at the exact straight elbows
+    assert host_emu.counter("lq") >= 16  # the guard took the LQ form
+    assert host_emu.counter("svd") >= 2  # and the Jacobi form at the exact straight elbows
     assert np.array_equal(conv, c["converged_exact"]) and np.array_equal(it, c["iters_exact"])
     assert (np.abs(q - c["q_exact"]).max(axis=1) <= tol_exact(c["cond0"])).all()
     well = c["cond0"] < 1e6
@@ -123,8 +98,8 @@ def test_lq_form_everywhere_reproduces_the_fixtures(emu, oracle_cases, monkeypat
     branch): the 96 oracle fixtures come out as with the closed form."""
     monkeypatch.setenv("IKG_SING_BETA", "0")
     c = oracle_cases
-    emu.lib.ikg_emu_lq_count(1)
+    host_emu.counter("lq")
     q, conv, it = emu(c["targets"], c["q0"])
-    assert emu.lib.ikg_emu_lq_count(1) == int(c["iters"].sum())
+    assert host_emu.counter("lq") == int(c["iters"].sum())
     assert np.array_equal(conv, c["converged"]) and np.array_equal(it, c["iters"])
     assert np.abs(q[conv] - c["q"][conv]).max() <= 1e-9

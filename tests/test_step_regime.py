@@ -12,18 +12,16 @@ against ik_oracle.computeqgrasppose(lam) in float64); group C keeps the
 gates of tests/test_gpu_parity.py.  The GPU suite (tests/
 test_gpu_step_regime.py) covers what exists on the device only: the wave-level
 selection, the packed and quad layouts and the collision term's kernels."""
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
+import emu as host_emu
 import helpers
 import step_regime_cases as sr
-from ikgrasp import _lib
 from ikgrasp.model import load_nextage
 
-EMU = helpers.emu_path()
 GENERIC = 99  # ikg_params.variant the emulator reads as "force the generic path"
 PATHS = ("rows_f64", "bcast_f64", "generic_f64", "damped_f64", "rows_f32")
 Q_GATE, ERR_GATE = 1e-9, 1e-10  # tests/test_gpu_parity.py
@@ -37,37 +35,25 @@ def fx():
 
 @pytest.fixture(scope="module")
 def emu():
-    if not os.path.exists(EMU):
-        pytest.skip("libikgrasp_emu.so not built")
-    lib = C.CDLL(EMU)
-    vp = C.c_void_p
-    lib.ikg_emu_solve.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp]
-    lib.ikg_emu_big_count.restype = C.c_longlong
-    desc = _lib.model_desc(load_nextage())
+    host_emu.load_or_skip()
+    model = load_nextage()
 
     def solve(path, targets, q0, **kw):
         """q0 [B, 15].  A broadcast path takes each problem with its row as the one shared q0."""
         dtype = 1 if path.endswith("f32") else 0
-        npt = np.float32 if dtype else np.float64
-        tg = np.ascontiguousarray(targets, dtype=npt).reshape(-1, 12)
-        B = len(tg)
-        q0 = np.ascontiguousarray(np.broadcast_to(q0, (B, 15)), dtype=npt)
+        tg = np.reshape(targets, (-1, 12))
+        q0 = np.broadcast_to(q0, (len(tg), 15))
         if path == "generic_f64":
             kw["variant"] = GENERIC
         if path == "damped_f64":
             kw["lambda_"] = sr.LAMBDA
-        p = _lib.default_params(**kw)
-        q, conv, it, err = np.empty((B, 15), npt), np.empty(B, np.uint8), np.empty(B, np.int32), np.empty((B, 2), npt)
-        lib.ikg_emu_big_count(1)
+        host_emu.counter("big")
         if path == "bcast_f64":
-            for i in range(B):
-                assert 0 == lib.ikg_emu_solve(C.byref(desc), dtype, tg[i].ctypes.data, q0[i].ctypes.data, 0, 1, C.byref(p),
-                                              q[i].ctypes.data, conv[i:].ctypes.data, it[i:].ctypes.data,
-                                              err[i].ctypes.data, None, 0, None)
+            q, conv, it, err = (np.concatenate(x) for x in zip(*[host_emu.solve(model, tg[i], q0[i], dtype, **kw)
+                                                                 for i in range(len(tg))]))
         else:
-            assert 0 == lib.ikg_emu_solve(C.byref(desc), dtype, tg.ctypes.data, q0.ctypes.data, 15, B, C.byref(p),
-                                          q.ctypes.data, conv.ctypes.data, it.ctypes.data, err.ctypes.data, None, 0, None)
-        return q.astype(np.float64), conv.astype(bool), it, err.astype(np.float64), int(lib.ikg_emu_big_count(1))
+            q, conv, it, err = host_emu.solve(model, tg, q0, dtype, **kw)
+        return q.astype(np.float64), conv, it, err.astype(np.float64), host_emu.counter("big")
 
     return solve
 

@@ -14,20 +14,16 @@
 * the IKG_EINVAL cases of ikg_trajectory_check_batch that return before any launch.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
-import helpers
 import trajcheck_cases as tc
 from ikgrasp import _lib
 from ikgrasp.collision import load_nextage_scene
 from ikgrasp.control import trajectory_ok
 from ikgrasp.model import load_nextage
 from ikgrasp.path import fold_segments, polyline_curves
-
-EMU = helpers.emu_path()
 
 
 @pytest.fixture(scope="module")
@@ -38,9 +34,8 @@ def cases():
 @pytest.fixture(scope="module")
 def answers(cases):
     """every group through the emulator once: {group index: answer}"""
-    # this file's subject is the emulator: a missing build is a failure, not a skip
-    assert os.path.exists(EMU), f"{EMU} not built (make -C <pkg>/csrc emu)"
-    run = tc.emu_runner(load_nextage(), load_nextage_scene(), EMU)
+    # this file's subject is the emulator: a missing build is a failure (emu.load()), not a skip
+    run = tc.emu_runner(load_nextage(), load_nextage_scene())
     out = {}
     for g in range(len(tc.group_names())):
         pts, t_min, t_max, mult, S, fixed = tc.group_inputs(g)

@@ -20,24 +20,23 @@ import types
 import numpy as np
 import pytest
 
-import helpers
+import emu as host_emu
 import trajdyn_oracle as to
 from ikgrasp import _lib, control
 from ikgrasp.model import (ActuatorLimits, load_nextage, load_nextage_actuation, load_nextage_inertia, parse_urdf)
 
-EMU = helpers.emu_path()
 NAMES = ["ref15", "fast", "torque_pos", "torque_neg", "static", "two", "spw5", "trio", "family", "five"]
 
 
 @pytest.fixture(scope="module")
 def runners():
     # this file's subject is the emulator: a missing build is a failure, not a skip
-    assert os.path.exists(EMU), f"{EMU} not built (make -C <pkg>/csrc emu)"
+    host_emu.load()
     cache = {}
 
     def get(model):
         if model not in cache:
-            cache[model] = to.emu_runner(*to.model_of(model), EMU)
+            cache[model] = to.emu_runner(*to.model_of(model))
         return cache[model]
 
     return get

@@ -7,27 +7,16 @@ From the exact (sin, cos) of a starting angle, Trig<double>::kResync = 128
 consecutive steps of d run with no resync -- the longest run the solve loop
 takes between two exact recomputations.  The bound is not a chosen figure: it
 is what the replaced form reaches on the same inputs, measured here."""
-import ctypes as C
-import os
-
 import numpy as np
 
-import helpers
+import emu as host_emu
 
-EMU = helpers.emu_path()
 STEPS = 128  # Trig<double>::kResync
 KINC = 0.025  # Trig<double>::kIncMax
 
 
 def _run(fn, d, a):
-    assert os.path.exists(EMU), "libikgrasp_emu.so not built"
-    lib = C.CDLL(EMU)
-    lib.ikg_emu_math.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    d = np.ascontiguousarray(d, dtype=np.float64)
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    out = np.empty(4 * len(d), dtype=np.float64)
-    assert lib.ikg_emu_math(fn, len(d), d.ctypes.data, a.ctypes.data, out.ctypes.data) == 0
-    return out.reshape(-1, 4)
+    return host_emu.math(fn, d, a).reshape(-1, 4)
 
 
 def _inputs():

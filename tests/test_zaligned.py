@@ -3,17 +3,14 @@ pose_error_f1<ZT>, selected per wave in ikg_solve.hpp pair_batch_body), on the
 CPU through the host emulator: the selection test itself, and that the form
 gives an aligned target the bits of the general one."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
-import helpers
+import emu as host_emu
 from ikgrasp import _lib
 from ikgrasp.model import load_nextage
 from ikgrasp.workload import uniform_targets
-
-EMU = helpers.emu_path()
 
 
 def _roll(tg, a):
@@ -27,15 +24,9 @@ def _roll(tg, a):
 
 @pytest.fixture(scope="module")
 def emu():
-    if not os.path.exists(EMU):
-        pytest.skip("libikgrasp_emu.so not built")
-    lib = C.CDLL(EMU)
-    vp = C.c_void_p
-    lib.ikg_emu_solve.argtypes = [vp, C.c_int, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, C.c_int, vp]
-    lib.ikg_emu_z_aligned.argtypes = [vp, C.c_int, vp, C.c_int64, vp]
-    lib.ikg_emu_force_general.argtypes = [C.c_int]
-    lib.ikg_emu_force_general.restype = None
-    desc = _lib.model_desc(load_nextage())
+    lib = host_emu.load_or_skip()
+    model = load_nextage()
+    desc = _lib.model_desc(model)
 
     def aligned(targets, dtype=0):
         npt = np.float64 if dtype == 0 else np.float32
@@ -45,24 +36,8 @@ def emu():
         return out.astype(bool)
 
     def solve(targets, q0, dtype=0, general=False, **kw):
-        npt = np.float64 if dtype == 0 else np.float32
-        tg = np.ascontiguousarray(targets, dtype=npt).reshape(-1, 12)
-        B = len(tg)
-        q0 = np.ascontiguousarray(q0, dtype=npt)
-        stride = 0 if q0.ndim == 1 else 15
-        p = _lib.default_params(**kw)
-        q = np.empty((B, 15), npt)
-        conv = np.empty(B, np.uint8)
-        it = np.empty(B, np.int32)
-        err = np.empty((B, 2), npt)
-        lib.ikg_emu_force_general(1 if general else 0)
-        try:
-            assert 0 == lib.ikg_emu_solve(C.byref(desc), dtype, tg.ctypes.data, q0.ctypes.data, stride, B, C.byref(p),
-                                          q.ctypes.data, conv.ctypes.data, it.ctypes.data, err.ctypes.data, None, 0,
-                                          None)
-        finally:
-            lib.ikg_emu_force_general(0)
-        return q, conv.astype(bool), it, err
+        with host_emu.forced(general=general):
+            return host_emu.solve(model, targets, q0, dtype, **kw)
 
     return dict(aligned=aligned, solve=solve)
 

@@ -197,15 +197,13 @@ def same_curve(a, ja, b, jb, keys=CURVE + SAMPLE):
 
 
 # ---------------------------------------------------------------- the emulator leg
-def emu_runner(model, scene, lib_path):
+def emu_runner(model, scene):
     """run(...) over ikg_emu_trajectory_check; rc != 0 raises ValueError"""
     import ctypes as C
 
+    import emu as host_emu
     from ikgrasp import _lib
-    lib = C.CDLL(lib_path)
-    vp = C.c_void_p
-    lib.ikg_emu_trajectory_check.argtypes = [vp, vp, vp, C.c_int64, vp, vp, C.c_int32, vp, vp]
-    lib.ikg_emu_trajectory_check.restype = C.c_int
+    lib = host_emu.load()
     md, cd = _lib.model_desc(model), _lib.collision_desc(scene)
     nq = model.nq
 

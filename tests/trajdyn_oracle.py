@@ -216,16 +216,14 @@ def same(a, ja, b, jb, keys=CURVE_KEYS + SAMPLE):
 
 
 # ---------------------------------------------------------------- the emulator leg
-def emu_runner(model, inertias, lib_path, gravity=do.GRAVITY):
+def emu_runner(model, inertias, gravity=do.GRAVITY):
     """run(points, t_min, t_max, mult, S, vlim, elim, samples_per_wave=0) over
     ikg_emu_trajectory_dynamics -> dict of every output; rc != 0 raises ValueError"""
     import ctypes as C
 
+    import emu as host_emu
     from ikgrasp import _lib
-    lib = C.CDLL(lib_path)
-    vp = C.c_void_p
-    lib.ikg_emu_trajectory_dynamics.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
-    lib.ikg_emu_trajectory_dynamics.restype = C.c_int
+    lib = host_emu.load()
     md, idesc = _lib.model_desc(model), _lib.inertia_desc(inertias, gravity)
     nq = model.nq
 
